@@ -3,7 +3,12 @@
 (space-time predictor Picard loop + volume integral + face Riemann solve +
 corrector) on 1/2/4/8 MI355X.
 
-    python bench.py --gpus N --steps K --warmup W [--config cfg2|cfg1|cfg4|fv-ref]
+    python bench.py --gpus N --steps K --warmup W [--config cfg2|cfg1|cfg4|fv-ref] [--full] [--dump-outputs DIR]
+
+A plain run sets up, warms up, times the K steps and prints the line.  --full adds what takes runs of its own: the CPU
+baselines (`cpu_baseline`, `cpu_reference_fv`) and, for cfg2 on one GPU, the short runs of the other configurations
+(`other_configs`).  --dump-outputs DIR writes the state the timed path handed its caller after its last step as
+DIR/<name>.npy (float64; a fixed seeded sample of whole cells / patches where the state is larger than the budget).
 
 --config cfg2 (default, the configuration BASELINE.json's metric is quoted on):
   N = 1 runs BASELINE.json configs[2] (128^3 cells, one GPU).  N > 1 keeps 128^3 cells per GPU
@@ -33,6 +38,7 @@ FP64_MEASURED_TFLOPS = 66.8 # bare v_fma_f64 loop on this chip (scripts/fp64_pea
                             # profiles/r01_stage_a_stamps.txt) -- reported beside the datasheet fraction, never instead of it
 HBM_PEAK_GBS = 8000.0       # MI355X_MICROARCH.md: 8.0 TB/s spec
 HBM_MEASURED_GBS = 6290.0   # ... and its measured float4-copy rate
+DUMP_BYTES = 48 << 20       # --dump-outputs: bytes of samples in all (with their headers the files stay below 64 MB)
 
 
 # ------------------------------------------------------------------------------------------------------
@@ -91,6 +97,27 @@ def synthetic_state(solver, part_coords, pdims, seed):
         s.u[..., v] = val * noise
     del phase, rho, E
     return 1.0 + (1.4 * 1.0 / 0.8) ** 0.5          # |u_d| + c_s upper bound per direction
+
+
+def dump_outputs(a, arrays, parts=1):
+    """--dump-outputs: arrays = {name: tensor [rows, ...]} (rows = cells or patches) as DIR/<name>.npy in float64.  Each gets
+    DUMP_BYTES / (parts * len(arrays)); a larger one is sampled by whole rows, a seeded choice kept in row order, so the same
+    arguments select the same entries in every run and every build."""
+    if not a.dump_outputs:
+        return
+    import numpy as np
+    import torch
+    os.makedirs(a.dump_outputs, exist_ok=True)
+    share = DUMP_BYTES // (parts * len(arrays))
+    for name, t in arrays.items():
+        rows = t.shape[0]
+        k = min(rows, share // (8 * max(1, t[0].numel())))
+        assert k > 0, "%s: one row is larger than the dump budget" % name
+        if k < rows:
+            g = torch.Generator().manual_seed(0)
+            idx = torch.randperm(rows, generator=g)[:k].sort().values
+            t = t[idx.to(t.device)]
+        np.save(os.path.join(a.dump_outputs, name + ".npy"), t.to(torch.float64).cpu().numpy())
 
 
 # ------------------------------------------------------------------------------------------------------
@@ -376,6 +403,7 @@ def run_cfg2(a, torch, exa, world, rank, local, pde=None):
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         el = float(t.item())
     finite = bool(torch.isfinite(s.u).all().item())
+    dump_outputs(a, {"u" if world == 1 else "u_rank%d" % rank: s.u.reshape((-1,) + tuple(s.u.shape[3:]))}, parts=world)
     dof_per_gpu = nc[0] * nc[1] * nc[2] * N ** 3 * 5
     out = {
         "metric": "DoF-updates/sec, 3D Euler p=%d fused STP+volume+Riemann, 1/2/4/8 MI355X" % a.order,
@@ -413,7 +441,7 @@ def run_cfg2(a, torch, exa, world, rank, local, pde=None):
                            "note": "fp64-compute-bound (48 FLOP/B): priced against the 78.6 TFLOP/s fp64 vector peak; the kernel "
                                    "issues no MFMA (fp64 MFMA has the same peak and fills 28 % of a tile at N = 6)"}
         out["roofline"].update(pmc)
-        if not a.no_cpu_baseline:
+        if a.full and not a.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline_dg(3, N, N)
             out["cpu_reference_fv"] = cpu_reference_fv()
     if sharded:
@@ -443,6 +471,7 @@ def run_cfg1(a, torch, exa, local):
     torch.cuda.synchronize()
     el = time.perf_counter() - t0
     tk = e0.elapsed_time(e1) / steps * 1e-3
+    dump_outputs(a, {"u": s.u.reshape((-1,) + tuple(s.u.shape[2:]))})
     dof = nc[0] * nc[1] * N * N * 5
     b_alg = 8 * 5 * (2 * N ** 2 + 8 * 2 * N) * nc[0] * nc[1]            # 3 840 B per cell
     traffic, src = read_traffic("traffic_cfg1.json")
@@ -461,7 +490,7 @@ def run_cfg1(a, torch, exa, local):
                         "compulsory_bytes_per_launch": 16 * 5 * N * N * nc[0] * nc[1],
                         "frac_of_compulsory": 16 * 5 * N * N * nc[0] * nc[1] / tk / 1e9 / HBM_PEAK_GBS,
                         "traffic": traffic, "traffic_source": src, "launch_ms": tk * 1e3, "bytes_per_launch": b_alg}}
-    if not a.no_cpu_baseline:
+    if a.full and not a.no_cpu_baseline:
         out["cpu_baseline"] = cpu_baseline_dg(2, N, 0, seconds=6.0)
     return out
 
@@ -519,6 +548,7 @@ def run_cfg4(a, torch, exa, world, rank, local, pde=None):
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         el = float(t.item())
     lim.check(wait=True)                                                   # (a step past the capacity would have kept the unlimited DG result)
+    dump_outputs(a, {"u" if world == 1 else "u_rank%d" % rank: s.u.reshape((-1,) + tuple(s.u.shape[3:]))}, parts=world)
     ta = sum(e0.elapsed_time(e1) for e0, e1 in s.stage_a_events) / steps * 1e-3
     work = s.work()
     dof = n ** 3 * N ** 3 * 5
@@ -561,7 +591,7 @@ def run_cfg4(a, torch, exa, world, rank, local, pde=None):
         if world > 1:
             dist.all_reduce(t, op=dist.ReduceOp.MAX)
         out["limiter_exchange_ms"] = float(t.item())
-    if not a.no_cpu_baseline and rank == 0 and world == 1:
+    if a.full and not a.no_cpu_baseline and rank == 0 and world == 1:
         out["cpu_baseline"] = cpu_baseline_dg(3, N, N, seconds=10.0)
     return out
 
@@ -593,6 +623,7 @@ def run_fv_ref(a, torch, exa, local):
     torch.cuda.synchronize()
     el = time.perf_counter() - t0
     tk = e0.elapsed_time(e1) / steps * 1e-3
+    dump_outputs(a, {"Q": Qs[warm + steps - 1]})
     Q = Qs
     vols = n * P * P
     b_alg = vols * (8 * V * (S / P) ** 2 + 8 * m)                       # patch + halo read once, n_real written once (220 B per volume)
@@ -610,7 +641,7 @@ def run_fv_ref(a, torch, exa, local):
                         "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": b_alg / tk / 1e9 / HBM_PEAK_GBS,
                         "frac_of_measured_copy": b_alg / tk / 1e9 / HBM_MEASURED_GBS, "traffic": traffic, "traffic_source": src,
                         "launch_ms": tk * 1e3, "bytes_per_launch": b_alg}}
-    if not a.no_cpu_baseline:
+    if a.full and not a.no_cpu_baseline:
         out["cpu_baseline"] = cpu_reference_fv()
     return out
 
@@ -636,6 +667,7 @@ def run_fv_grid(a, torch, exa, local):
         fv.invalidate()
         n_patches = int(torch.tensor(grid).prod())
         vols = n_patches * P ** dim
+        U_rows = (-1,) + tuple(U.shape[dim:])                           # one row per patch
         S = P + 2
         b_alg = vols * 16 * V                                        # every state read once, written once (halo-less arrays)
         b_bare = vols * (8 * V * (S / P) ** dim + 8 * 5)             # the bare kernel on the reference layout: patch + halo read, n_real written
@@ -669,6 +701,8 @@ def run_fv_grid(a, torch, exa, local):
             fv.step(min(0.05 * dt, 0.2 * fv.h / dim / lam))
         timed(cfl_step, 2)
         t_full = timed(cfl_step, steps)
+        dump_outputs(a, {"U_" + {"ref-4x4": "ref_4x4", "limiter-15^3": "limiter_15cubed"}[name]: fv.interior_device().reshape(U_rows)},
+                     parts=len(shapes))
         out_shapes[name] = {"patches": n_patches, "patch_size": P, "variables": V, "bare_kernel_ms": 1e3 * t_bare, "grid_step_ms": 1e3 * t_step,
                             "cfl_scan_ms": 1e3 * t_cfl, "step_with_cfl_ms": 1e3 * t_full, "step_with_cfl_over_bare": t_full / t_bare,
                             "grid_step_over_bare": t_step / t_bare, "two_pass_torch_fill_ms": 1e3 * t_two,
@@ -711,9 +745,13 @@ def main():
     ap.add_argument("--config", default="cfg2", choices=["cfg2", "cfg1", "cfg4", "fv-ref", "fv-grid", "cfg2_sympy", "cfg4_sympy"])
     ap.add_argument("--cells", type=int, default=128, help="cells per axis per GPU (default: BASELINE configs[2])")
     ap.add_argument("--order", type=int, default=5)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what takes runs of its own: the CPU baselines and (cfg2 on one GPU) the other configurations")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the state the timed path computed in its last step as DIR/<name>.npy (float64, at most 64 MB in all)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: leave out the CPU baselines")
     ap.add_argument("--no-other-configs", action="store_true",
-                    help="cfg2 on one GPU: do not append the short cfg1 / cfg4 / fv-ref runs (`other_configs`) to the line")
+                    help="with --full, cfg2 on one GPU: do not append the short cfg1 / cfg4 / fv-ref runs (`other_configs`) to the line")
     ap.add_argument("--no-reserve-trial", action="store_true", help="sharded runs: skip the warm-up trial of reserve_cus 0 / 8")
     ap.add_argument("--backend", default="nccl", help="rehearsal only: 'gloo' runs the multi-rank path with host-staged exchange")
     ap.add_argument("--share-gpu", action="store_true", help="rehearsal only: every rank uses cuda:0")
@@ -766,7 +804,7 @@ def main():
 
     if a.config == "cfg2":
         out = run_cfg2(a, torch, exa, world, rank, local)
-        if world == 1 and not a.self_exchange and not a.no_other_configs:
+        if a.full and world == 1 and not a.self_exchange and not a.no_other_configs:
             # the other rows of SURVEY.md 8(d), briefly, in the same (driver-run) invocation: value, ms per step and roofline of each;
             # metric / value / config of the line stay those of cfg 2
             import gc
@@ -774,6 +812,7 @@ def main():
             torch.cuda.empty_cache()
             b = argparse.Namespace(**vars(a))
             b.no_cpu_baseline = True
+            b.dump_outputs = None                                  # (the outputs are the headline path's)
             b.steps, b.warmup = 3, 1
             others = {}
             b2 = argparse.Namespace(**vars(b))

@@ -32,7 +32,7 @@ print(json.dumps(rec))
 PY
 }
 echo "== bench lines"; 
-python3 bench.py --steps 20 --warmup 5 > $OUT/bench_cfg2.json 2> $OUT/bench_cfg2.err; tail -c 600 $OUT/bench_cfg2.json; echo
+python3 bench.py --steps 20 --warmup 5 --full > $OUT/bench_cfg2.json 2> $OUT/bench_cfg2.err; tail -c 600 $OUT/bench_cfg2.json; echo
 python3 bench.py --gpus 1 --self-exchange --steps 5 --warmup 2 --no-cpu-baseline > $OUT/bench_cfg2_self_exchange.json 2> $OUT/bench_cfg2_self_exchange.err; tail -c 400 $OUT/bench_cfg2_self_exchange.json; echo
 python3 bench.py --config cfg4 --gpus 1 --self-exchange --steps 5 --warmup 2 --no-cpu-baseline > $OUT/bench_cfg4_self_exchange.json 2> $OUT/bench_cfg4_self_exchange.err; tail -c 400 $OUT/bench_cfg4_self_exchange.json; echo
 for cfg in cfg1 cfg4 fv-ref fv-grid cfg2_sympy cfg4_sympy; do python3 bench.py --config $cfg --steps 10 --warmup 3 --no-cpu-baseline > $OUT/bench_$cfg.json 2> $OUT/bench_$cfg.err; tail -c 300 $OUT/bench_$cfg.json; echo; done

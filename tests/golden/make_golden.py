@@ -97,17 +97,8 @@ def main():
         out[name] = len(code)
 
     # 3-D, multi-patch variant of the Batched_stateless body (dim=3,P=15,H=1,n_patches=2)
-    from sympy.codegen.ast import integer, real, none
-    k3 = pkg.KernelBuilder(dim=3, patch_size=15, halo_size=1, n_real=5, n_aux=0, n_patches=2)
-    Q = k3.item('Q'); Qc = k3.item('Q_copy'); tf = k3.directional_item('tmp_flux'); te = k3.directional_item('tmp_eigen', struct=False)
-    dt = k3.const('dt'); normal = k3.directional_const('normal', [0, 1, 2])
-    Flux = k3.function('Flux', parameter_types=[Q, real, Q], return_type=integer)
-    Eigen = k3.function('maxEigenvalue', parameter_types=[Q, real], return_type=real)
-    Max = k3.function('max', parameter_types=[Q, Q], return_type=none)
-    k3.single(Qc[0], Q[0]); k3.directional(Flux(Qc[0], normal, tf[0])); k3.directional(te[0], Eigen(Qc[0], normal))
-    k3.directional(Qc[0], Qc[0] + 0.5 * (tf[-1] - tf[1]))
-    left = -Max(te[-1], te[0]) * (Q[0] - Q[-1]); right = -Max(te[1], te[0]) * (Q[0] - Q[1])
-    k3.directional(Qc[0], Qc[0] + 0.5 * dt * (left - right), struct=True); k3.single(Q[0], Qc[0])
+    from tests.ref_examples import batched_stateless_statements
+    k3 = batched_stateless_statements(pkg.KernelBuilder, dim=3, patch_size=15, n_aux=0, n_patches=2, normal=(0, 1, 2))
     with open(os.path.join(HERE, "builder_state_3d_p15.json"), "w") as f:
         json.dump(builder_state(k3), f, indent=1, sort_keys=True)
     with open(os.path.join(HERE, "cppprinter_3d_p15.txt"), "w") as f:
@@ -194,6 +185,16 @@ def main():
     with open(os.path.join(HERE, "fv_ref2d_random.json"), "w") as f:
         json.dump(dict(source="oracle/_ref time_step, dt=0.37; compare cells (i,j) in {2,3}^2, vars 0..3 only (SURVEY F6)",
                        dt=0.37, Q_in=Qb.tolist(), Q_out_valid=Qo[:, 2:4, 2:4, 0:4].tolist()), f)
+
+    # the input of tests/test_oracle_pinning.py::test_fv_faithful_vs_compiled_reference_live through time_step: defined outputs + aux
+    from tests.util import euler_ref2d_patches
+    Ql = euler_ref2d_patches(16, 6, 10, seed=11)
+    Qlo = Ql.copy()
+    for pidx in range(16):
+        tmp = np.ascontiguousarray(Qlo[pidx]).ravel()
+        R.ref_time_step(tmp, 0.21)
+        Qlo[pidx] = tmp.reshape(6, 6, 10)
+    np.savez(os.path.join(HERE, "fv_ref2d_seed11.npz"), dt=0.21, Q_in=Ql, Q_out_valid=Qlo[:, 2:4, 2:4, 0:4], Q_out_aux=Qlo[..., 5:])
     print("golden written:", sorted(os.listdir(HERE)))
     print("mask", list(mask), "n_passthrough", len(passthrough), "n_undefined", int((~stable).sum()))
 

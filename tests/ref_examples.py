@@ -2,7 +2,9 @@
 
 * `reference_example(...)` runs the body of one of the reference's OWN example scripts where it lies under
   /root/reference (lines exec'ed in place, nothing copied; same pattern as tests/golden/make_golden.py) against
-  the KernelBuilder it is given.  Tests that need it skip where the reference tree is absent (the GPU box).
+  the KernelBuilder it is given.  Where the reference tree is absent, `batched_stateless` is built by
+  `batched_stateless_statements(...)` instead (the statement list tests/golden/make_golden.py builds the 3-D
+  fixture from); tests of the other example skip there.
 * `rusanov_patch_update(...)` / `cell_data_patch_update(...)` hold the STATEMENT LISTS of the reference's examples
   (`examples/Batched_stateless.py:9-35`, `examples/kernel-generator.py:6-45`) with other variable names and free
   dim / sizes: the statement list is the input the HIP back-end's recogniser has to match, so it is the same
@@ -29,6 +31,8 @@ def reference_example(name, KernelBuilder, ctor=None, substitutions=()):
     ctor: replacement text for the constructor arguments (the script's own are dim=2, patch_size=4, ...);
     substitutions: (old, new) text pairs applied to the body (e.g. the per-direction constant for dim = 3)."""
     if not have_reference():
+        if name == "batched_stateless" and ctor is None and not substitutions:
+            return batched_stateless_statements(KernelBuilder)
         pytest.skip("reference tree not present (its example scripts are exec'ed where they lie, never copied)")
     path, first, last = EXAMPLES[name]
     lines = open(os.path.join(REF, path)).read().split("\n")[first - 1:last]
@@ -44,8 +48,27 @@ def reference_example(name, KernelBuilder, ctor=None, substitutions=()):
     return env["kernel"]
 
 
+def batched_stateless_statements(KernelBuilder, dim=2, patch_size=4, halo_size=1, n_real=5, n_aux=5, n_patches=1, normal=(0, 1)):
+    """The statement list of `examples/Batched_stateless.py` with its names: tests/golden/make_golden.py captures the 3-D fixtures by
+    running it on the reference's own KernelBuilder, and `reference_example("batched_stateless")` stands on it where the reference
+    tree is absent.  Its expected outputs are those captured from the reference."""
+    k = KernelBuilder(dim=dim, patch_size=patch_size, halo_size=halo_size, n_real=n_real, n_aux=n_aux, n_patches=n_patches)
+    Q = k.item('Q'); Qc = k.item('Q_copy'); tf = k.directional_item('tmp_flux'); te = k.directional_item('tmp_eigen', struct=False)
+    dt = k.const('dt'); normal = k.directional_const('normal', list(normal))
+    Flux = k.function('Flux', parameter_types=[Q, real, Q], return_type=integer)
+    Eigen = k.function('maxEigenvalue', parameter_types=[Q, real], return_type=real)
+    Max = k.function('max', parameter_types=[Q, Q], return_type=none)
+    k.single(Qc[0], Q[0]); k.directional(Flux(Qc[0], normal, tf[0])); k.directional(te[0], Eigen(Qc[0], normal))
+    k.directional(Qc[0], Qc[0] + 0.5 * (tf[-1] - tf[1]))
+    left = -Max(te[-1], te[0]) * (Q[0] - Q[-1]); right = -Max(te[1], te[0]) * (Q[0] - Q[1])
+    k.directional(Qc[0], Qc[0] + 0.5 * dt * (left - right), struct=True); k.single(Q[0], Qc[0])
+    return k
+
+
 def reference_example_3d_p15(KernelBuilder):
     """The 3-D, two-patch variant the fixture builder_state_3d_p15.json was captured for."""
+    if not have_reference():
+        return batched_stateless_statements(KernelBuilder, dim=3, patch_size=15, n_aux=0, n_patches=2, normal=(0, 1, 2))
     return reference_example("batched_stateless", KernelBuilder, ctor="dim=3,patch_size=15,halo_size=1,n_real=5,n_aux=0,n_patches=2",
                              substitutions=(("'normal',[0,1]", "'normal',[0,1,2]"),))
 

@@ -35,6 +35,50 @@ def test_gpus_must_match_world_size():
     assert r.returncode != 0 and "WORLD_SIZE" in r.stderr
 
 
+def test_dump_outputs_samples_whole_rows_within_budget(tmp_path):
+    """--dump-outputs: an array larger than its share is sampled by whole rows (cells, patches) -- the same rows in every run, in row order --
+    a small one is written whole, everything as float64 and below 64 MB in all; without the option nothing is written."""
+    import argparse
+    import numpy as np
+    import torch
+    import bench
+    big = torch.arange(20000 * 512, dtype=torch.float64).reshape(20000, 8, 64)            # 80 MB
+    small = torch.rand(10, 3, dtype=torch.float32)
+    for d in ("a", "b"):
+        bench.dump_outputs(argparse.Namespace(dump_outputs=str(tmp_path / d)), {"big": big, "small": small})
+    got, again = np.load(tmp_path / "a" / "big.npy"), np.load(tmp_path / "b" / "big.npy")
+    assert got.dtype == np.float64 and got.shape[1:] == (8, 64) and 0 < got.shape[0] < 20000
+    assert np.array_equal(got, again)
+    rows = (got[:, 0, 0] // 512).astype(int)
+    assert np.all(np.diff(rows) > 0) and np.array_equal(got, big.numpy()[rows])
+    assert np.array_equal(np.load(tmp_path / "a" / "small.npy"), small.double().numpy())
+    assert sum(f.stat().st_size for f in (tmp_path / "a").iterdir()) <= 64 << 20
+    bench.dump_outputs(argparse.Namespace(dump_outputs=None), {"big": big})
+    assert sorted(p.name for p in tmp_path.iterdir()) == ["a", "b"]
+
+
+@pytest.mark.gpu
+def test_plain_line_is_lean_and_dumps_the_state(tmp_path):
+    """A plain run times exactly --steps steps and carries no CPU baseline and no other configuration; --dump-outputs writes the state
+    after the last timed step, the same in two runs with the same arguments."""
+    import numpy as np
+    outs = []
+    for d in ("a", "b"):
+        r = subprocess.run([sys.executable, BENCH, "--gpus", "1", "--cells", "8", "--steps", "3", "--warmup", "1", "--dump-outputs",
+                            str(tmp_path / d)], env=_env(), capture_output=True, text=True, timeout=900)
+        assert r.returncode == 0, r.stderr[-3000:]
+        lines = r.stdout.splitlines()
+        assert len(lines) == 1 and lines[0].startswith("{"), r.stdout
+        outs.append(json.loads(lines[0]))
+    out = outs[0]
+    assert out["steps"] == 3 and out["warmup"] == 1 and out["ms_per_step"] > 0 and out["finite"]
+    assert abs(out["value"] * out["ms_per_step"] * 1e-3 / (8 ** 3 * 6 ** 3 * 5) - 1) < 1e-9
+    assert "cpu_baseline" not in out and "cpu_reference_fv" not in out and "other_configs" not in out
+    u = np.load(tmp_path / "a" / "u.npy")
+    assert u.dtype == np.float64 and u.shape == (8 ** 3, 6, 6, 6, 5) and np.isfinite(u).all()
+    assert np.array_equal(u, np.load(tmp_path / "b" / "u.npy"))
+
+
 @pytest.mark.gpu
 @pytest.mark.parametrize("gpus", [2, 4])
 def test_self_launched_ranks_share_one_gpu_over_gloo(gpus):
@@ -83,7 +127,7 @@ def test_cfg4_on_two_ranks_and_rooflines_on_sharded_lines():
 
 @pytest.mark.gpu
 def test_single_gpu_line_has_roofline_and_config_variants():
-    r = subprocess.run([sys.executable, BENCH, "--cells", "16", "--steps", "2", "--warmup", "1", "--no-cpu-baseline"], env=_env(),
+    r = subprocess.run([sys.executable, BENCH, "--cells", "16", "--steps", "2", "--warmup", "1", "--full", "--no-cpu-baseline"], env=_env(),
                        capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-3000:]
     out = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][0])
