@@ -279,7 +279,7 @@ def step_xt(u, dt, dx, ops, pde, t=0.0, origin=None, n_it=None, stages=False):
             elif b == a:
                 sh = [1] * (2 * d - 1)
                 sh[a] = grid[a]
-                xf.append((origin[a] + (np.arange(grid[a]) + 1.0) * dx[a]).reshape(sh))
+                xf.append((origin[a] + (np.arange(grid[a], dtype=u.dtype) + 1) * dx[a]).reshape(sh))
             else:
                 xf.append(np.squeeze(x3[b], axis=d + a))               # node axis a removed
         qm, Fm = qR, FR
@@ -293,7 +293,7 @@ def step_xt(u, dt, dx, ops, pde, t=0.0, origin=None, n_it=None, stages=False):
         xlo = list(xf)
         sh = [1] * (2 * d - 1)
         sh[a] = grid[a]
-        xlo[a] = (origin[a] + np.arange(grid[a]) * dx[a]).reshape(sh)
+        xlo[a] = (origin[a] + np.arange(grid[a], dtype=u.dtype) * dx[a]).reshape(sh)
         qm_l, qp_l = np.roll(qR, 1, axis=a), qL                       # low face of every cell: minus = left neighbour's R, plus = own L
         lam_l = np.maximum(pde.maxeig(qm_l, xlo, tf, a) * np.ones(qL.shape[:-1]), pde.maxeig(qp_l, xlo, tf, a) * np.ones(qL.shape[:-1]))
         s_l = lam_l.max(axis=tuple(range(d, d + d - 1)), keepdims=True) if d > 1 else lam_l

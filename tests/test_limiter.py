@@ -8,7 +8,8 @@ import oracle
 from oracle import aderdg_numpy as A
 from oracle.dg_operators import operators
 from oracle.limiter_numpy import apply_all_axes, limited_step, projection_matrix, reconstruction_matrix
-from tests.util import euler_dg_state, rel_err
+from tests import dg_cases as C
+from tests.util import assert_dg_parity, euler_dg_state, rel_err
 
 
 @pytest.mark.parametrize("N", [2, 3, 4, 6, 8])
@@ -54,31 +55,38 @@ def test_subcell_limiter_refuses_cells_of_unequal_size():
     exa.SubcellLimiter(exa.AderDgSolver(2, 3, (2, 2), dx=[0.5, 0.5])).step(1e-3, mask)
 
 
+def _limited_ref(u, mask, dt, dx, N, n_it, steps=2):
+    dim = len(dx)
+    ref = u.copy()
+    for _ in range(steps):
+        ref = limited_step(ref, mask, dt, dx, operators(N), A.Euler(), _fv(dim, 5, oracle.PDE_EULER), n_it)
+    return ref
+
+
+@pytest.mark.parametrize("dim,N,nc", C.LIMITER_CASES)     # (3, 8): cfg 4's order: level-streamed stage A + 17^3 slab FV update + reconstruction
+def test_limited_step_cases_see_the_last_iteration(dim, N, nc):
+    """CPU: at the CFL-0.9 step the GPU test below can tell the limited step from the one with a Picard iteration less."""
+    u, dx, dt, mask = C.limiter_input(dim, N, nc)
+    ref = _limited_ref(u, mask, dt, dx, N, N)
+    assert_dg_parity(ref, ref, u, _limited_ref(u, mask, dt, dx, N, N - 1), what="limited steps")
+
+
 @pytest.mark.gpu
-@pytest.mark.parametrize("dim,N,nc", [(2, 4, (4, 3)), (3, 3, (2, 2, 3)), (2, 2, (3, 3)),
-                                       (3, 8, (2, 1, 2)),        # cfg 4's order: level-streamed stage A + 17^3 slab FV update + reconstruction
-                                       (3, 7, (1, 2, 2))])
+@pytest.mark.parametrize("dim,N,nc", C.LIMITER_CASES)
 def test_limited_step_vs_oracle(dim, N, nc):
     from exahype_amd import solvers as exa
     ops = operators(N)
-    u = euler_dg_state(tuple(nc) + (N,) * dim, seed=31 + N)
-    dx = [1.0 / nc[0]] * dim                                    # uniform cells (the FV patch has one h)
-    dt = 0.02 * dx[0] / (2 * N - 1)
-    rng = np.random.default_rng(5)
-    mask = rng.random(nc) < 0.35
-    mask.flat[0] = True
+    u, dx, dt, mask = C.limiter_input(dim, N, nc)             # uniform cells (the FV patch has one h)
     s = exa.AderDgSolver(dim, N, nc, dx=dx)
     lim = exa.SubcellLimiter(s)
     P, R = lim.operators()
     Po = projection_matrix(ops["xi"], 2 * N - 1)
     assert np.max(np.abs(P - Po)) < 1e-13 and np.max(np.abs(R - reconstruction_matrix(Po, ops["w"]))) < 1e-12
     s.upload(u)
-    ref = u.copy()
     for _ in range(2):
         n = lim.step(dt, mask)
         assert n == int(mask.sum())
-        ref = limited_step(ref, mask, dt, dx, ops, A.Euler(), _fv(dim, 5, oracle.PDE_EULER))
-    assert rel_err(s.download(), ref) < 1e-10
+    assert_dg_parity(s.download(), _limited_ref(u, mask, dt, dx, N, N), u, _limited_ref(u, mask, dt, dx, N, N - 1), what="limited steps")
     # untroubled cells are exactly the DG result, troubled cells differ from it
     s2 = exa.AderDgSolver(dim, N, nc, dx=dx); s2.upload(u); s2.step(dt)
     s.upload(u); lim.step(dt, mask)
