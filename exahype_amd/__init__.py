@@ -5,5 +5,6 @@ hand-written HIP kernels behind the C-ABI of include/exahype_hip.h, reached
 through `exahype_amd.printers.HIPPrinter` or `exahype_amd.solvers`."""
 from .KernelBuilder import KernelBuilder
 from .TypedFunction import TypedFunction
+from .boundary import Dirichlet, Outflow, Wall
 
-__all__ = ["KernelBuilder", "TypedFunction"]
+__all__ = ["KernelBuilder", "TypedFunction", "Outflow", "Wall", "Dirichlet"]

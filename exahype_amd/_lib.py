@@ -52,6 +52,7 @@ SIGNATURES = {
     "exa_dg_has_corrector_predictor": (C.c_int, [_vp]),
     "exa_dg_corrector_predictor": (C.c_int, [_vp, _vp, _vp, _vp, C.POINTER(_vp), _lp, _lp, C.c_double, C.c_double, _dp, _vp, _vp]),
     "exa_dg_pack_face": (C.c_int, [_vp, _vp, C.c_int, C.c_int, _vp, _vp]),
+    "exa_dg_boundary_ghost": (C.c_int, [_vp, _vp, C.c_int, C.c_int, C.c_int, _dp, _vp, C.c_double, _vp, _vp, _vp]),
     "exa_lim_operators": (C.c_int, [_vp, _vp, _vp]),
     "exa_lim_patch_count": (C.c_long, [_vp]),
     "exa_dg_project_patches": (C.c_int, [_vp, _vp, _vp, C.c_long, _vp, _vp]),

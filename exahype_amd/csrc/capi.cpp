@@ -88,6 +88,7 @@ struct exa_dg_plan {
     long nc[3], ncells;
     const DgLaunchTable* tab;
     DgOpsHost ops;
+    double idx[3];         // 1 / dx of the last stage A: where exa_dg_boundary_ghost places the face nodes of a Dirichlet datum
 };
 
 extern "C" {
@@ -350,6 +351,7 @@ int exa_dg_plan_create(int device, int dim, int N, int n_vars, int pde, int n_pi
     p->ops.stage_a_reserve = 0;
     p->ops.origin[0] = p->ops.origin[1] = p->ops.origin[2] = 0.0;
     p->ops.time = 0.0;
+    p->idx[0] = p->idx[1] = p->idx[2] = 0.0;
     p->ops.stage_a_variant = EXA_STAGE_A_AUTO;
     if (const char* ev = getenv("EXA_STAGE_A")) {
         if (!strcmp(ev, "lds")) p->ops.stage_a_variant = EXA_STAGE_A_LDS;
@@ -469,6 +471,7 @@ int exa_dg_predictor_volume_box(exa_dg_plan* p, double* u_dev, double* trace_dev
     if (rc) return rc;
     double idx[3];
     inv_dx(p, dx, idx);
+    for (int d = 0; d < 3; d++) p->idx[d] = idx[d];
     return p->tab->stage_a(p->N, u_dev, u_dev, trace_dev, p->ncells, &box, dt, idx, p->n_it, &p->ops, (hipStream_t)stream);
 }
 
@@ -566,6 +569,29 @@ int exa_dg_pack_face(exa_dg_plan* p, const double* trace_dev, int d, int side, d
     EXA_HIP(hipMemcpy2DAsync(buf_dev, (size_t)inner * TS * sizeof(double), src, (size_t)p->nc[d] * inner * TS * sizeof(double),
                              (size_t)inner * TS * sizeof(double), (size_t)outer, hipMemcpyDeviceToDevice, (hipStream_t)stream));
     return EXA_OK;
+}
+
+int exa_dg_boundary_ghost(exa_dg_plan* p, const double* trace_dev, int d, int side, int kind, const double* coeff, const double* states_dev,
+                          double dt, double* ghost_dev, double* lambda_dev, void* stream) {
+    if (!p || !ghost_dev) { set_error("exa_dg_boundary_ghost: NULL plan or ghost_dev"); return EXA_ERR_INVALID; }
+    if (d < 0 || d >= p->dim || side < 0 || side > 1) { set_error("exa_dg_boundary_ghost: face (d %d, side %d) outside a %d-D block", d, side, p->dim); return EXA_ERR_INVALID; }
+    if (kind != EXA_BC_OUTFLOW && kind != EXA_BC_WALL && kind != EXA_BC_DIRICHLET) {
+        set_error("exa_dg_boundary_ghost: kind %d (EXA_BC_OUTFLOW | EXA_BC_WALL | EXA_BC_DIRICHLET)", kind);
+        return EXA_ERR_INVALID;
+    }
+    if (kind != EXA_BC_DIRICHLET && (!trace_dev || !coeff)) { set_error("exa_dg_boundary_ghost: outflow / wall need trace_dev and the 2*n_vars factors coeff"); return EXA_ERR_INVALID; }
+    if (kind != EXA_BC_DIRICHLET && (states_dev || lambda_dev)) { set_error("exa_dg_boundary_ghost: states_dev / lambda_dev belong to EXA_BC_DIRICHLET"); return EXA_ERR_INVALID; }
+    if (kind == EXA_BC_DIRICHLET && !states_dev && !coeff) { set_error("exa_dg_boundary_ghost: Dirichlet needs states_dev or the constant state coeff"); return EXA_ERR_INVALID; }
+    if (kind == EXA_BC_DIRICHLET && states_dev && coeff) { set_error("exa_dg_boundary_ghost: Dirichlet takes states_dev or coeff, not both"); return EXA_ERR_INVALID; }
+    if (kind == EXA_BC_DIRICHLET && (exa_pde_flags(p->pde) & EXA_PDE_FLAG_XT) && !(p->idx[0] > 0.0)) {
+        set_error("exa_dg_boundary_ghost: the face nodes of this term set need the cell size of a stage A (exa_dg_predictor_volume) first");
+        return EXA_ERR_INVALID;
+    }
+    if (!p->tab->boundary) { set_error("exa_dg_boundary_ghost: the kernels of pde %d carry no boundary entry (rebuild its library)", p->pde); return EXA_ERR_INVALID; }
+    int rc = use_device(p->device);
+    if (rc) return rc;
+    return p->tab->boundary(p->N, trace_dev, p->ncells, p->nc, d, side, kind, coeff, states_dev, dt, &p->ops, p->idx, ghost_dev, lambda_dev,
+                            (hipStream_t)stream) == 0 ? EXA_OK : EXA_ERR_HIP;
 }
 
 /* ---- FV subcell limiter glue ------------------------------------------------------ */

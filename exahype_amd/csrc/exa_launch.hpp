@@ -57,6 +57,11 @@ struct DgLaunchTable {
     // fused single-stage periodic step u_in -> u_out (2-D, n_picard = 0; exa_dg_fused.hpp), or nullptr
     int (*fused_single)(int N, const double* u_in, double* u_out, const long* nc, double dt, const double* idx,
                         const DgOpsHost* ops, hipStream_t s);
+    // ghost[d*2+side] from a domain boundary condition (exa_dg_boundary.hpp; capi.cpp exa_dg_boundary_ghost): kind EXA_BC_OUTFLOW / _WALL
+    // scale the block's own outward trace at that face by coeff[2 nv]; EXA_BC_DIRICHLET averages states[t][y][N][nv] over the Gauss time
+    // levels (states null: the constant state coeff[nv]) and folds their largest eigenvalue into lam (if not null)
+    int (*boundary)(int N, const double* trace, long ncells, const long* nc, int d, int side, int kind, const double* coeff, const double* states,
+                    double dt, const DgOpsHost* ops, const double* idx, double* ghost, double* lam, hipStream_t s);
 };
 // returns nullptr when (dim, pde) is not built
 const DgLaunchTable* dg_launch_table(int dim, int pde);

@@ -587,7 +587,7 @@ struct UserPDE {
     def key(self):
         h = hashlib.sha256(self.source().encode())
         for f in ("dg_inst.hip", "fv_rusanov.hip", "exa_dg_kernels.hpp", "exa_dg_stream.hpp", "exa_dg_reg.hpp", "exa_dg_fused.hpp",
-                  "exa_dg_common.hpp", "exa_launch.hpp", "exa_pde.hpp", "exa_dg_plain.hpp", "exa_dg_m8.hpp"):
+                  "exa_dg_common.hpp", "exa_launch.hpp", "exa_pde.hpp", "exa_dg_plain.hpp", "exa_dg_m8.hpp", "exa_dg_boundary.hpp"):
             h.update(open(os.path.join(CSRC, f), "rb").read())
         h.update(open(os.path.join(os.path.dirname(os.path.abspath(__file__)), "build.py"), "rb").read())      # (compiler flags)
         h.update(repr(self.dg_flags).encode())

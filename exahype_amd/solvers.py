@@ -15,6 +15,7 @@ import numpy as np
 
 from . import _lib
 from ._lib import (FV_FAITHFUL, FV_RUSANOV, PDE_ADVECTION, PDE_EULER, PDE_EULER_REF2D, check, darr, larr)
+from .boundary import Dirichlet, Outflow, Wall, coefficients as _bc_coefficients, validate_boundary
 
 
 def _torch():
@@ -184,6 +185,11 @@ class CartesianPartition:
     def partitioned(self, d):
         return self.pdims[d] > 1 or d in self.exchange_self
 
+    def domain_face(self, d, side):
+        """True if this rank's block face (d, side) lies on the domain boundary: the process grid has extent 1 along d (the RCCL-to-self
+        rehearsal of exchange_self included) or the rank sits at that end of it."""
+        return self.pdims[d] == 1 or self.coords[d] == (0 if side == 0 else self.pdims[d] - 1)
+
     def shell_and_interior(self, nc):
         """Disjoint cell boxes: the layers touching a partitioned block face, and the rest."""
         dim = self.dim
@@ -314,9 +320,12 @@ class AderDgSolver:
     u     : CUDA tensor [nc0, nc1, (nc2,) N, N, (N,) n_vars]   (reference AoS layout)
     trace : CUDA tensor [dim, 2, nc0, nc1, nc2, 2*n_vars*N^(dim-1)]
 
-    With `part` (CartesianPartition) the block is one shard of a periodic global
-    grid: stage A runs on the boundary shell first, the face traces travel over
-    RCCL on a second stream while the interior cells run stage A, stage B follows.
+    With `part` (CartesianPartition) the block is one shard of a global grid: stage A
+    runs on the boundary shell first, the face traces travel over RCCL on a second
+    stream while the interior cells run stage A, stage B follows.
+
+    boundary         {(axis, side): Outflow() | Wall(sign) | Dirichlet(state)} (exahype_amd.boundary): the ghost traces at those faces of the
+                     domain come from the condition (exa_dg_boundary_ghost) instead of the periodic wrap; faces not named stay periodic.
 
     stage_a          "auto" | "lds" | "reg": which stage-A kernel serves 3-D N = 6 / N = 8 (include/exahype_hip.h EXA_STAGE_A_*)
     one_kernel_step  True: Riemann solve + corrector of a step run in front of the next step's predictor (3-D, N = 6, "reg"); step() then
@@ -328,8 +337,12 @@ class AderDgSolver:
     STAGE_A = {"auto": 0, "lds": 1, "reg": 2}      # include/exahype_hip.h EXA_STAGE_A_*
 
     def __init__(self, dim, N, ncells, pde=PDE_EULER, n_vars=5, n_picard=-1, dx=None, device=0, part=None,
-                 backend_is_gloo=False, fused_single_stage=True, stage_a="auto", reserve_cus=None, one_kernel_step=False, origin=None, time=0.0):
+                 backend_is_gloo=False, fused_single_stage=True, stage_a="auto", reserve_cus=None, one_kernel_step=False, origin=None, time=0.0,
+                 boundary=None):
         torch = _torch()
+        self.boundary = validate_boundary(boundary, dim, n_vars, pde)
+        if self.boundary and one_kernel_step:
+            raise ValueError("one_kernel_step: not built for a domain with boundary conditions (the fused kernel reads periodic / halo ghosts only)")
         self.lib = _lib.load()
         self.dim, self.N, self.nv, self.pde = dim, N, n_vars, pde
         self.nc = [int(c) for c in ncells]
@@ -366,7 +379,7 @@ class AderDgSolver:
         self._trace2 = None
         self.part = part
         self.halo = None
-        self._fused = bool(fused_single_stage) and bool(self.lib.exa_dg_has_fused_step(h))
+        self._fused = bool(fused_single_stage) and bool(self.lib.exa_dg_has_fused_step(h)) and not self.boundary    # (periodic only)
         self._u2 = None
         # measurement hooks (bench.py): stage_a_events collects one (start, end) event pair per stage-A launch on the
         # launching stream; exchange_events one (shell done, comm start, comm end, interior start, interior end, pack end) tuple
@@ -384,6 +397,107 @@ class AderDgSolver:
             self.comm_stream = torch.cuda.Stream(device=self.dev, priority=-1)
             self.set_reserve_cus(int(os.environ.get("EXA_RESERVE_CUS", "0")) if reserve_cus is None else int(reserve_cus))
             self.shell, self.interior = part.shell_and_interior(self.nc)
+        self._setup_boundary()
+
+    def _setup_boundary(self):
+        """Per domain face of this block with a condition: its ghost buffer [transverse cells][ts] and what fills it."""
+        torch = _torch()
+        self._bc = []                     # (d, side, condition, host factors or None, ghost buffer)
+        self._lam_bc = None               # Dirichlet functions: largest eigenvalue of the states of the last step (device)
+        self._lam_bc_valid = False        # ... left there by a step (before the first one run() evaluates f itself)
+        self._lam_bc_const = None         # constant Dirichlet states: host maximum, applied as a clamp in run()
+        for (d, side), bc in sorted(self.boundary.items()):
+            if self.part is not None and not self.part.domain_face(d, side):
+                continue
+            nt = int(np.prod(self.nc)) // self.nc[d]
+            buf = torch.zeros(nt, self.ts, dtype=torch.float64, device=self.dev)
+            coeff = _bc_coefficients(bc, self.nv)
+            self._bc.append((d, side, bc, None if coeff is None else darr(list(coeff)), buf))
+            if isinstance(bc, Dirichlet) and not bc.constant and self._lam_bc is None:
+                self._lam_bc = torch.zeros(1, dtype=torch.float64, device=self.dev)
+        const = [np.asarray(bc.state) for bc in self.boundary.values() if isinstance(bc, Dirichlet) and bc.constant]
+        if const:
+            b = np.stack(const)
+            self._lam_bc_const = max(float(np.max(pde_eval(self.pde, d, b)[1])) for d in range(self.dim))
+        self._bc_const_done = False       # constant Dirichlet ghosts of term sets that do not see x, t: filled once
+        self._bc_x = {}                   # (d, side) -> face node positions [transverse cells * Nf][3] (Dirichlet functions)
+        self._xi_host = self.operators()["xi"]
+
+    def face_positions(self, d, side):
+        """[transverse cells * N^(dim-1)][3] physical coordinates of the nodes of the block face (d, side), in the order of a ghost buffer
+        (transverse cells lexicographic over the other axes, then the face nodes): where a Dirichlet function is evaluated."""
+        torch = _torch()
+        key = (d, side)
+        if key not in self._bc_x:
+            xi = torch.as_tensor(self.operators()["xi"], dtype=torch.float64, device=self.dev)
+            others = [a for a in range(self.dim) if a != d]
+            k = len(others)
+            shape = tuple(self.nc[a] for a in others) + (self.N,) * k
+            X = torch.zeros(shape + (3,), dtype=torch.float64, device=self.dev)
+            for j, a in enumerate(others):
+                cs, ns = [1] * (2 * k), [1] * (2 * k)
+                cs[j], ns[k + j] = self.nc[a], self.N
+                c = torch.arange(self.nc[a], dtype=torch.float64, device=self.dev).reshape(cs)
+                X[..., a] = self.origin[a] + (c + xi.reshape(ns)) * self.dx[a]
+            X[..., d] = self.origin[d] + (self.nc[d] if side else 0) * self.dx[d]
+            self._bc_x[key] = X.reshape(-1, 3).contiguous()
+        return self._bc_x[key]
+
+    def _dirichlet_states(self, bc, d, side, times):
+        """f at the face nodes of (d, side) and the given times: [transverse cells][Nf][len(times)][n_vars] (device, contiguous)"""
+        torch = _torch()
+        X = self.face_positions(d, side)
+        q = [torch.as_tensor(bc.state(X, float(t)), dtype=torch.float64, device=self.dev).reshape(X.shape[0], self.nv) for t in times]
+        return torch.stack(q, dim=1).contiguous()
+
+    def fill_boundary(self, dt):
+        """The ghost traces of this block's domain faces for the step [time, time + dt] (after stage A: outflow and walls read its traces)."""
+        if not self._bc:
+            return
+        xt = _sees_position_and_time(self.lib, self.pde)
+        if self._lam_bc is not None:
+            self._lam_bc.zero_()
+        xi = self._xi_host if self._lam_bc is not None else None
+        for d, side, bc, coeff, buf in self._bc:
+            states, lam = None, None
+            if isinstance(bc, Dirichlet):
+                if bc.constant:
+                    if self._bc_const_done and not xt:
+                        continue
+                else:
+                    states = self._dirichlet_states(bc, d, side, [self.time + x * dt for x in xi])
+                    lam = self._lam_bc
+            check(self.lib.exa_dg_boundary_ghost(self._plan, C.c_void_p(self.trace.data_ptr()), d, side, bc.kind, coeff,
+                                                 C.c_void_p(states.data_ptr()) if states is not None else None, dt, C.c_void_p(buf.data_ptr()),
+                                                 C.c_void_p(lam.data_ptr()) if lam is not None else None, _stream_ptr()))
+        self._bc_const_done = True
+
+    def ghost_ptrs(self):
+        """The six ghost pointers of stage B: a domain face with a condition -> its boundary buffer; else a partitioned direction -> the halo
+        ghost; else NULL (periodic wrap in the block)."""
+        if not self._bc:
+            return self.halo.ghost_ptrs() if self.halo is not None else None
+        arr = self.halo.ghost_ptrs() if self.halo is not None else (C.c_void_p * 6)()
+        for d, side, _, _, buf in self._bc:
+            arr[d * 2 + side] = buf.data_ptr()
+        return arr
+
+    def boundary_eigenvalue(self, lam):
+        """lam (1-element device tensor): the CFL eigenvalue with the Dirichlet states taken in -- constant states as a clamp, functions
+        by the eigenvalue the boundary kernel left for the last step (before the first step: f at the face nodes at the current time)."""
+        if self._lam_bc_const is not None:
+            lam = lam.clamp(min=self._lam_bc_const)
+        if self._lam_bc is not None:
+            if not self._lam_bc_valid:
+                torch = _torch()
+                self._lam_bc.zero_()
+                for d, side, bc, _, _ in self._bc:
+                    if isinstance(bc, Dirichlet) and not bc.constant:
+                        q = self._dirichlet_states(bc, d, side, [self.time]).reshape(-1, self.nv)
+                        self._lam_bc.copy_(torch.maximum(self._lam_bc, _max_eigenvalue_at(self.lib, self.pde, self.dim, q,
+                                                                                          self.face_positions(d, side), self.time)))
+            lam = _torch().maximum(lam, self._lam_bc)
+        return lam
 
     def set_reserve_cus(self, workgroups):
         """Keep the persistent stage-A grids `workgroups` below the resident count (CUs left to RCCL's transport kernels while the interior
@@ -478,7 +592,7 @@ class AderDgSolver:
     def riemann_corrector(self, dt, lo=None, hi=None, lam_out=None):
         """Stage B on the box (default: the whole block).  lam_out (1-element float64 CUDA tensor): the launch also leaves the largest eigenvalue of
         the corrected u there -- the next step's CFL scan without a pass of its own (exa_dg_riemann_corrector_cfl; not for term sets that see x, t)."""
-        ghosts = self.halo.ghost_ptrs() if self.halo is not None else None
+        ghosts = self.ghost_ptrs()
         self._where_and_when()
         lo_, hi_ = (larr(lo) if lo is not None else None), (larr(hi) if hi is not None else None)
         if lam_out is not None:
@@ -527,8 +641,10 @@ class AderDgSolver:
                                                 C.c_void_p(self.halo.send[d * 2 + side].data_ptr()), _stream_ptr()))
 
     def step(self, dt):
-        """One ADER-DG time step of the block (periodic, or one shard of a periodic grid); advances `time`."""
+        """One ADER-DG time step of the block (or of one shard of the grid); advances `time`."""
         self._step(dt)
+        if self._lam_bc is not None:
+            self._lam_bc_valid = True         # (the step's boundary kernel left the eigenvalue of its Dirichlet states)
         self.time += dt
 
     def _step(self, dt):
@@ -553,6 +669,7 @@ class AderDgSolver:
                 self._pending_dt = dt
                 return
             self.predictor_volume(dt)
+            self.fill_boundary(dt)
             self.riemann_corrector(dt, lam_out=self._cfl_out)
             return
         # (one-kernel step on a shard: the shell cells' kernel reads the ghosts the PREVIOUS step received -- complete, every step ends
@@ -592,6 +709,7 @@ class AderDgSolver:
             self.halo.finish()
             if timed:
                 c1.record()
+        self.fill_boundary(dt)                         # (after both boxes of stage A; on the compute stream)
         cur.wait_stream(self.comm_stream)
         if self._one_kernel:
             self._pending_dt = dt
@@ -843,6 +961,8 @@ def _dg_run(self, t_end, cfl=0.4, max_steps=1000000):
         while self.time < t_end * (1 - 1e-14) and steps < max_steps:
             if lam is None:
                 lam = self.max_eigenvalue()
+            if self.boundary:
+                lam = self.boundary_eigenvalue(lam)
             if self.part is not None and self.part.world > 1:
                 import torch.distributed as dist
                 dist.all_reduce(lam, op=dist.ReduceOp.MAX)
@@ -868,7 +988,11 @@ class SubcellLimiter:
 
     On a sharded grid (solver.part) two small exchanges precede the projection: the troubled flags of the blocks'
     boundary layers, then -- only where the cell across the face is troubled -- the adjacent subcell layer of the
-    boundary cells; the patches of troubled cells at a block face take their halo from those."""
+    boundary cells; the patches of troubled cells at a block face take their halo from those.
+
+    At a domain face with a boundary condition (AderDgSolver(boundary=...)) the ghost subcell layer is the boundary cell's own adjacent
+    layer (exa_lim_face_layers), unchanged for Outflow, times the sign for a Wall, and the prescribed state at the ghost subcells' centres
+    at the step's start time for Dirichlet; the DMP neighbourhood of detect() does not reach across such a face."""
 
     DEFAULT_FRACTION = 0.1          # default capacity: this share of the block's cells (at least 16)
 
@@ -904,6 +1028,10 @@ class SubcellLimiter:
         self._ovf_event = torch.cuda.Event()
         self._ovf_event.record(torch.cuda.current_stream(solver.dev))
         self.hx_mask = self.hx_layer = None
+        self._bc_layers = {}              # (d, side) -> ghost subcell layer [transverse cells][Ns^(dim-1)][n_vars] of a domain face
+        for d, side, _, _, _ in solver._bc:
+            nt = ncell // solver.nc[d]
+            self._bc_layers[(d, side)] = torch.zeros((nt, self.Ns ** (solver.dim - 1), solver.nv), dtype=torch.float64, device=solver.dev)
         if solver.halo is not None:
             stage = solver.halo.stage
             self.hx_mask = HaloExchange(solver.part, solver.nc, 1, solver.dev, stage_through_host=stage)
@@ -954,11 +1082,53 @@ class SubcellLimiter:
                 other = [s.nc[a] for a in range(dim) if a != d]
                 up.select(d, s.nc[d] - 1).copy_(ghost[d * 2 + 1].reshape(other))
                 dn.select(d, 0).copy_(ghost[d * 2 + 0].reshape(other))
+            for side in range(2):                              # a domain face with a condition: no neighbour, the cell's own mean
+                if (d, side) in self._bc_layers:
+                    edge = 0 if side == 0 else s.nc[d] - 1
+                    (dn if side == 0 else up).select(d, edge).copy_(mean.select(d, edge))
             lo = torch.minimum(lo, torch.minimum(up, dn))
             hi = torch.maximum(hi, torch.maximum(up, dn))
         span = (hi - lo).clamp_min(floor)
         bad |= (rho.amax(nodes) > hi + dmp_tol * span) | (rho.amin(nodes) < lo - dmp_tol * span)
         return bad
+
+    def subcell_ghost_positions(self, d, side):
+        """[transverse cells * Ns^(dim-1)][3] centres of the ghost subcells beyond the domain face (d, side), in the layer order"""
+        torch = _torch()
+        s, Ns = self.s, self.Ns
+        others = [a for a in range(s.dim) if a != d]
+        k = len(others)
+        X = torch.zeros(tuple(s.nc[a] for a in others) + (Ns,) * k + (3,), dtype=torch.float64, device=s.dev)
+        sub = (torch.arange(Ns, dtype=torch.float64, device=s.dev) + 0.5) / Ns
+        for j, a in enumerate(others):
+            cs, ns = [1] * (2 * k), [1] * (2 * k)
+            cs[j], ns[k + j] = s.nc[a], Ns
+            c = torch.arange(s.nc[a], dtype=torch.float64, device=s.dev).reshape(cs)
+            X[..., a] = s.origin[a] + (c + sub.reshape(ns)) * s.dx[a]
+        X[..., d] = s.origin[d] + ((s.nc[d] + 0.5 / Ns) if side else -0.5 / Ns) * s.dx[d]
+        return X.reshape(-1, 3)
+
+    def _boundary_layers(self, ghosts):
+        """The ghost subcell layers of the domain faces with a condition into the pointer array (ghosts: the exchanged ones, or None)."""
+        torch = _torch()
+        s = self.s
+        if not self._bc_layers:
+            return ghosts
+        arr = ghosts if ghosts is not None else (C.c_void_p * 6)()
+        for d, side, bc, _, _ in s._bc:
+            buf = self._bc_layers[(d, side)]
+            if isinstance(bc, Dirichlet):
+                if bc.constant:
+                    buf.copy_(torch.as_tensor(bc.state, dtype=torch.float64, device=s.dev).expand_as(buf))
+                else:
+                    X = self.subcell_ghost_positions(d, side)
+                    buf.copy_(torch.as_tensor(bc.state(X, float(s.time)), dtype=torch.float64, device=s.dev).reshape(buf.shape))
+            else:
+                check(s.lib.exa_lim_face_layers(s._plan, C.c_void_p(s.u.data_ptr()), d, side, None, C.c_void_p(buf.data_ptr()), _stream_ptr()))
+                if isinstance(bc, Wall):
+                    buf.mul_(torch.as_tensor(bc.sign, dtype=torch.float64, device=s.dev))
+            arr[d * 2 + side] = buf.data_ptr()
+        return arr
 
     def _exchange_subcell_layers(self, m):
         """m: troubled flags of the block, float64 [nc0, nc1, nc2] on the device.  Returns the ghost-layer pointer array."""
@@ -1022,6 +1192,7 @@ class SubcellLimiter:
             if self.exchange_events is not None:
                 e1.record(torch.cuda.current_stream(s.dev))
                 self.exchange_events.append((e0, e1))
+        ghosts = self._boundary_layers(ghosts)
         patches = self._patches
         check(s.lib.exa_dg_project_patches_ghost(s._plan, C.c_void_p(s.u.data_ptr()), C.c_void_p(cells.data_ptr()), cap,
                                                  C.c_void_p(patches.data_ptr()), ghosts, _stream_ptr()))

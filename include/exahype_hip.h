@@ -227,6 +227,26 @@ int exa_dg_corrector_predictor(exa_dg_plan* plan, double* u_dev, const double* t
  * to the low neighbour, which uses it as ghost_dev[d*2+1]); side 1 -> R traces
  * of the cells with c_d == ncells[d]-1 (-> the high neighbour's ghost_dev[d*2+0]). */
 int exa_dg_pack_face(exa_dg_plan* plan, const double* trace_dev, int d, int side, double* buf_dev, void* stream);
+/* Domain boundaries: fill ghost_dev with the state beyond the block face (d, side) that a boundary condition prescribes, in the
+ * layout exa_dg_pack_face writes, ghost_dev[transverse cell][2*n_vars*Nf] with the entry (field*n_vars + v)*Nf + y (field 0 =
+ * time-averaged state, 1 = time-averaged normal flux; transverse cells lexicographic over the other axes, the last fastest;
+ * exa_dg_face_count(plan, d) doubles).  The result is a valid ghost_dev[d*2+side] for exa_dg_riemann_corrector[_cfl] of the same step.
+ *   EXA_BC_OUTFLOW    ghost = the block's own outward traces at that face (trace_dev after stage A; coeff = 2*n_vars factors, all 1:
+ *                     then bit-identical to exa_dg_pack_face(plan, trace_dev, d, side)); the Rusanov flux becomes F(q_in).
+ *   EXA_BC_WALL       the same gather with coeff = (s, -s): ghost state s (.) qbar_in, ghost flux -s (.) Fbar_in (s[n_vars] = +-1).  Exact
+ *                     (a mirror image of the block across the face) for term sets with F_d(S q) = -S F_d(q), S = diag(s); for Euler s
+ *                     negates the normal momentum, variable 1 + d.
+ *   EXA_BC_DIRICHLET  ghost = sum_l w_l (q_l, F_d(q_l, x_y, t_l)) over the Gauss time levels t_l = t + xi_l dt of the step (t: the
+ *                     time of exa_dg_plan_set_origin_time), with the states states_dev[transverse cell][Nf][N][n_vars] (device) at the
+ *                     face nodes x_y (origin + cell size of the last exa_dg_predictor_volume); or, with states_dev NULL, the constant state
+ *                     coeff[n_vars] (host) at every node and time.  lambda_dev (device, may be NULL) receives max(*lambda_dev, the largest
+ *                     eigenvalue of those states over the directions): not zeroed here, so several faces fold into one scalar.
+ * Outflow / wall take no states_dev and no lambda_dev; wrong arguments return EXA_ERR_INVALID with a message. */
+#define EXA_BC_OUTFLOW 1
+#define EXA_BC_WALL 2
+#define EXA_BC_DIRICHLET 3
+int exa_dg_boundary_ghost(exa_dg_plan* plan, const double* trace_dev, int d, int side, int kind, const double* coeff,
+                          const double* states_dev, double dt, double* ghost_dev, double* lambda_dev, void* stream);
 /* FV subcell limiter glue (BASELINE configs[4]): N_s = 2N-1 subcells per axis.
  * exa_lim_operators: host copies of the projection P[N_s][N] and the mean-preserving least-squares
  * reconstruction R[N][N_s].  exa_dg_project_patches: for the n cells listed in cells_dev build FV patches
