@@ -57,6 +57,36 @@ def operators(N):
                 F0=phiL.copy(), K1=K1, iK1=iK1)
 
 
+def gauss_legendre_mp(N, dps):
+    """Gauss-Legendre nodes and weights on [0, 1] as mpmath numbers (call inside mpmath.workdps(dps)): Newton on P_N (three-term recurrence)
+    from the fp64 nodes; w_i = 1 / ((1 - x_i^2) P_N'(x_i)^2) (half the [-1, 1] weight 2 / (...))."""
+    import mpmath
+    mp = mpmath.mpf
+
+    def legendre(x):
+        p0, p1 = mp(1), x
+        if N == 0:
+            return p0, mp(0)
+        for k in range(2, N + 1):
+            p0, p1 = p1, ((2 * k - 1) * x * p1 - (k - 1) * p0) / k
+        return p1, N * (x * p1 - p0) / (x * x - 1)           # P_N, P_N'
+
+    x0, _ = np.polynomial.legendre.leggauss(N)
+    xs, ws = [], []
+    for g in x0:
+        x = mp(float(g))
+        for _ in range(100):
+            p, dp = legendre(x)
+            dx = p / dp
+            x -= dx
+            if abs(dx) < mp(10) ** (-dps - 2):
+                break
+        p, dp = legendre(x)
+        xs.append((x + 1) / 2)
+        ws.append(1 / ((1 - x * x) * dp * dp))
+    return xs, ws
+
+
 _HP_CACHE = {}
 
 
@@ -64,35 +94,13 @@ def operators_hp(N, dps=40):
     """The operators of `operators(N)` built in mpmath at `dps` digits from closed forms and returned as np.longdouble
     (cached per N): the high-precision reference the fp64 oracles are pinned against (tests/test_dg_reference_hp.py).
 
-    Nodes: Newton on P_N (three-term recurrence) from the fp64 nodes; weights on [0, 1]: w_i = 1 / ((1 - x_i^2) P_N'(x_i)^2)
-    (half the [-1, 1] weight 2 / (...)); D from barycentric weights; iK1 by an mpmath inverse."""
+    Nodes and weights: gauss_legendre_mp; D from barycentric weights; iK1 by an mpmath inverse."""
     if N in _HP_CACHE:
         return _HP_CACHE[N]
     import mpmath
     with mpmath.workdps(dps):
         mp = mpmath.mpf
-
-        def legendre(x):
-            p0, p1 = mp(1), x
-            if N == 0:
-                return p0, mp(0)
-            for k in range(2, N + 1):
-                p0, p1 = p1, ((2 * k - 1) * x * p1 - (k - 1) * p0) / k
-            return p1, N * (x * p1 - p0) / (x * x - 1)           # P_N, P_N'
-
-        x0, _ = np.polynomial.legendre.leggauss(N)
-        xs, ws = [], []
-        for g in x0:
-            x = mp(float(g))
-            for _ in range(100):
-                p, dp = legendre(x)
-                dx = p / dp
-                x -= dx
-                if abs(dx) < mp(10) ** (-dps - 2):
-                    break
-            p, dp = legendre(x)
-            xs.append((x + 1) / 2)
-            ws.append(1 / ((1 - x * x) * dp * dp))
+        xs, ws = gauss_legendre_mp(N, dps)
         bw = [mp(1)] * N
         for j in range(N):
             for k in range(N):

@@ -7,6 +7,7 @@ N_s = 2p+1 equal subcells per axis, constrained least-squares reconstruction, an
 Reference anchor: none -- /root/reference holds no limiter; "parity unpinned".  The FV
 patch update used inside IS the reference's kernel shape (`Unit test/test.cpp`, corrected form).
 Pinned by the identities in tests/test_limiter.py (R P = I on degree <= p data, mean preservation).
+P and R are pinned to the mpmath operators of oracle/limiter_reference.py (tests/test_limiter_reference.py).
 """
 import numpy as np
 

@@ -35,7 +35,8 @@ VARIANT_N8_CASES = [((1, 2, 2), -1), ((2, 1, 1), 1), ((2, 2, 1), 3), ((7, 7, 6),
 ONE_KERNEL_CASES = [((2, 2, 2), -1), ((1, 1, 1), 2), ((3, 2, 1), 1), ((1, 3, 2), 3), ((9, 8, 8), -1)]
 ONE_KERNEL_DT_FACTORS = (1.0, 0.7, 1.2, 0.9)     # of the CFL-0.6 step (STEPS_CFL)
 # tests/test_limiter.py::test_limited_step_vs_oracle
-LIMITER_CASES = [(2, 4, (4, 3)), (3, 3, (2, 2, 3)), (2, 2, (3, 3)), (3, 8, (2, 1, 2)), (3, 7, (1, 2, 2))]
+LIMITER_CASES = [(2, 4, (4, 3)), (3, 3, (2, 2, 3)), (2, 2, (3, 3)), (3, 8, (2, 1, 2)), (3, 7, (1, 2, 2)),
+                 (2, 5, (3, 2)), (3, 5, (2, 1, 2)), (2, 6, (2, 3)), (3, 6, (1, 2, 2))]      # N = 5, 6: limited steps at the orders no other case launches
 # tests/test_dg_hard_states.py: one case per stage-A kernel (label, dim, N, nc, stage_a, fused 2-D single stage)
 HARD_KERNELS = [("lds_n4", 3, 4, (2, 2, 3), "auto", False), ("reg_n6", 3, 6, (2, 2, 2), "reg", False), ("stream_n7", 3, 7, (2, 1, 2), "auto", False),
                 ("m8_n8", 3, 8, (1, 2, 2), "reg", False), ("fused_2d_n4", 2, 4, (5, 3), "auto", True)]

@@ -115,3 +115,11 @@ def euler_scaled_state(shape, seed, scale):
     """euler_dg_state times `scale` (2^-20, 2^20): the same flow (Euler is homogeneous of degree 1), every conserved variable far from 1 --
     the device's fast reciprocal of rho sees values it was never measured on."""
     return euler_dg_state(shape, seed) * scale
+
+
+def log_limiter_measurement(kind, **fields):
+    """Measurement aid of tests/test_limiter_kernels.py, like EXA_DG_ERR_LOG above: with EXA_LIM_ERR_LOG=<file> every comparison appends one JSON line
+    (kind: operators | projection | ghost | face_layers | reconstruction | round_trip; the largest error / bound ratio it saw)."""
+    if os.environ.get("EXA_LIM_ERR_LOG"):
+        with open(os.environ["EXA_LIM_ERR_LOG"], "a") as f:
+            f.write(json.dumps(dict(kind=kind, test=os.environ.get("PYTEST_CURRENT_TEST", ""), **fields)) + "\n")
