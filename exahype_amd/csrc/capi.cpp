@@ -661,6 +661,32 @@ int exa_dg_reconstruct_patches(exa_dg_plan* p, const double* patch_dev, const lo
                                static_cast<const double*>(p->ops.lim) + (size_t)p->N * Ns, (hipStream_t)stream);
 }
 
+int exa_lim_snapshot(exa_dg_plan* p, const double* u_dev, double* u_old_dev, double* bounds_dev, void* stream) {
+    if (!p || !u_dev || !bounds_dev || u_dev == u_old_dev) { set_error("exa_lim_snapshot: bad argument (plan, u_dev or bounds_dev is NULL, or u_old_dev == u_dev)"); return EXA_ERR_INVALID; }
+    int rc = use_device(p->device);
+    if (rc) return rc;
+    return limiter_snapshot(p->dim, p->N, p->nv, p->ncells, u_dev, u_old_dev, bounds_dev, (hipStream_t)stream);
+}
+
+int exa_lim_detect(exa_dg_plan* p, const double* u_cand_dev, const double* bounds_dev, const double* const* ghost_bounds_dev,
+                   const int* face_kind, double d0, double eps, double floor, unsigned char* mask_dev, void* stream) {
+    if (!p || !u_cand_dev || !bounds_dev || !mask_dev) { set_error("exa_lim_detect: NULL argument"); return EXA_ERR_INVALID; }
+    int rc = use_device(p->device);
+    if (rc) return rc;
+    if (p->nv < 2) { set_error("exa_lim_detect: needs a density and an energy (n_vars >= 2), the plan has %d", p->nv); return EXA_ERR_INVALID; }
+    if (!(d0 >= 0.0) || !(eps >= 0.0) || floor != floor) { set_error("exa_lim_detect: d0 and eps must be >= 0 and floor a number"); return EXA_ERR_INVALID; }
+    LimGhosts gb{};
+    for (int f = 0; f < 2 * p->dim; f++) {
+        const int kind = face_kind ? face_kind[f] : EXA_LIM_FACE_PERIODIC;
+        if (kind < EXA_LIM_FACE_PERIODIC || kind > EXA_LIM_FACE_NONE) { set_error("exa_lim_detect: face_kind[%d] = %d", f, kind); return EXA_ERR_INVALID; }
+        if (kind == EXA_LIM_FACE_GHOST) {
+            if (!ghost_bounds_dev || !ghost_bounds_dev[f]) { set_error("exa_lim_detect: face %d is EXA_LIM_FACE_GHOST without ghost bounds", f); return EXA_ERR_INVALID; }
+            gb.layer[f] = ghost_bounds_dev[f];
+        }
+    }
+    return limiter_detect(p->dim, p->N, p->nv, p->nc, u_cand_dev, bounds_dev, &gb, face_kind, d0, eps, floor, mask_dev, (hipStream_t)stream);
+}
+
 int exa_dg_max_eigenvalue(exa_dg_plan* p, const double* u_dev, double* lambda_dev, void* stream) {
     if (!p || !u_dev || !lambda_dev) { set_error("exa_dg_max_eigenvalue: NULL argument"); return EXA_ERR_INVALID; }
     int rc = use_device(p->device);

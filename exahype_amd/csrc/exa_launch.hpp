@@ -31,6 +31,10 @@ int limiter_face_layers(int dim, int N, int Ns, int nv, const long* nc, const do
                         double* out, const double* Pdev, hipStream_t s);
 int limiter_reconstruct(int dim, int N, int Ns, int nv, const double* patch, const long* cells, long n, double* u,
                         const double* Rdev, hipStream_t s);
+// a-posteriori detection: u^n -> u_old (may be null) + bounds[cell][4]; candidate + bounds (+ neighbour blocks' bounds) -> mask bytes
+int limiter_snapshot(int dim, int N, int nv, long ncells, const double* u, double* u_old, double* bounds, hipStream_t s);
+int limiter_detect(int dim, int N, int nv, const long* nc, const double* u, const double* bounds, const LimGhosts* ghosts, const int* kinds,
+                   double d0, double eps, double floor, unsigned char* mask, hipStream_t s);
 
 struct StageBBox {
     long nc[3], lo[3], nb[3];

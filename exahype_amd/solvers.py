@@ -983,8 +983,13 @@ AderDgSolver.run = _dg_run
 # ----------------------------------------------------------------------------------------------
 class SubcellLimiter:
     """Limited ADER-DG step: untroubled cells take the DG step, troubled cells the FV Rusanov patch update
-    (patch_size 2p+1, halo 1 -- the reference's kernel shape) of their projected data.  The troubled mask is an
-    input (synthetic Bernoulli mask in the benchmark; a physical detector is host logic outside this path).
+    (patch_size 2p+1, halo 1 -- the reference's kernel shape) of their projected data.  step(dt, mask) takes the troubled
+    mask as an input (synthetic Bernoulli mask in the benchmark; detect() is an a-priori indicator in torch ops on the state before
+    the step).  step_a_posteriori(dt) and run(t_end) find the mask themselves, on the device and AFTER the DG step (MOOD): the DG
+    candidate is checked against u^n (exa_lim_snapshot / exa_lim_detect: positivity, finiteness, a relaxed discrete maximum principle
+    on density and energy) and the troubled cells are redone from u^n with the FV patch update.  That order matters: the a-priori
+    loop detect(u^n) -> step leaves the admissible states on a Sod tube at p = 5 (negative density at 16 cells), the a-posteriori one
+    stays positive at p = 3, 5, 7.
 
     On a sharded grid (solver.part) two small exchanges precede the projection: the troubled flags of the blocks'
     boundary layers, then -- only where the cell across the face is troubled -- the adjacent subcell layer of the
@@ -1108,12 +1113,15 @@ class SubcellLimiter:
         X[..., d] = s.origin[d] + ((s.nc[d] + 0.5 / Ns) if side else -0.5 / Ns) * s.dx[d]
         return X.reshape(-1, 3)
 
-    def _boundary_layers(self, ghosts):
-        """The ghost subcell layers of the domain faces with a condition into the pointer array (ghosts: the exchanged ones, or None)."""
+    def _boundary_layers(self, ghosts, u=None, t=None):
+        """The ghost subcell layers of the domain faces with a condition into the pointer array (ghosts: the exchanged ones, or None).
+        u, t: the state the layers are taken from and the time of the Dirichlet data (default: the solver's current ones)."""
         torch = _torch()
         s = self.s
         if not self._bc_layers:
             return ghosts
+        u = s.u if u is None else u
+        t = s.time if t is None else t
         arr = ghosts if ghosts is not None else (C.c_void_p * 6)()
         for d, side, bc, _, _ in s._bc:
             buf = self._bc_layers[(d, side)]
@@ -1122,17 +1130,19 @@ class SubcellLimiter:
                     buf.copy_(torch.as_tensor(bc.state, dtype=torch.float64, device=s.dev).expand_as(buf))
                 else:
                     X = self.subcell_ghost_positions(d, side)
-                    buf.copy_(torch.as_tensor(bc.state(X, float(s.time)), dtype=torch.float64, device=s.dev).reshape(buf.shape))
+                    buf.copy_(torch.as_tensor(bc.state(X, float(t)), dtype=torch.float64, device=s.dev).reshape(buf.shape))
             else:
-                check(s.lib.exa_lim_face_layers(s._plan, C.c_void_p(s.u.data_ptr()), d, side, None, C.c_void_p(buf.data_ptr()), _stream_ptr()))
+                check(s.lib.exa_lim_face_layers(s._plan, C.c_void_p(u.data_ptr()), d, side, None, C.c_void_p(buf.data_ptr()), _stream_ptr()))
                 if isinstance(bc, Wall):
                     buf.mul_(torch.as_tensor(bc.sign, dtype=torch.float64, device=s.dev))
             arr[d * 2 + side] = buf.data_ptr()
         return arr
 
-    def _exchange_subcell_layers(self, m):
-        """m: troubled flags of the block, float64 [nc0, nc1, nc2] on the device.  Returns the ghost-layer pointer array."""
+    def _exchange_subcell_layers(self, m, u=None):
+        """m: troubled flags of the block, float64 [nc0, nc1, nc2] on the device; u: the state the layers are projected from (default:
+        the solver's).  Returns the ghost-layer pointer array."""
         s, hm, hl = self.s, self.hx_mask, self.hx_layer
+        u = s.u if u is None else u
         nc3 = s.nc + [1] * (3 - s.dim)
         for d in range(s.dim):
             if s.part.partitioned(d):
@@ -1145,7 +1155,7 @@ class SubcellLimiter:
                 continue
             for side in range(2):
                 # ghost[d*2+side] = flags of the cells across my face (d, side): where set, they need my layer
-                check(s.lib.exa_lim_face_layers(s._plan, C.c_void_p(s.u.data_ptr()), d, side,
+                check(s.lib.exa_lim_face_layers(s._plan, C.c_void_p(u.data_ptr()), d, side,
                                                 C.c_void_p(hm.ghost[d * 2 + side].data_ptr()),
                                                 C.c_void_p(hl.send[d * 2 + side].data_ptr()), _stream_ptr()))
         hl.start()
@@ -1161,17 +1171,31 @@ class SubcellLimiter:
         `capacity` cannot be served: `self.overflow` (0-dim CUDA bool) says so -- see check()."""
         torch = _torch()
         s = self.s
-        # the FV patch update takes ONE volume size h (the reference's generated `time_step` has no cell size at all: SURVEY.md Appendix B): a grid with
-        # different cell sizes per axis would get a silently wrong update -- refused (as in oracle/limiter_numpy.py, which restates this glue)
-        if max(s.dx) - min(s.dx) > 1e-12 * max(s.dx):
-            raise ValueError("SubcellLimiter.step: the FV patch update takes one volume size, the grid has dx = %s; use cells of equal size per axis" % (list(s.dx),))
+        self._one_volume_size("step")
         self.check()                                           # a COMPLETED earlier step past the capacity raises here (no synchronisation)
         if isinstance(mask, torch.Tensor):
             m = mask.to(device=s.dev, dtype=torch.bool)
         else:
             m = torch.as_tensor(np.ascontiguousarray(mask), dtype=torch.bool).to(s.dev, non_blocking=True)
         m = m.reshape(-1)
-        ncell, cap = m.numel(), self.capacity
+        count = self._compact(m)
+        self._project(m, s.u, s.time)
+        t0 = s.time
+        s.step(dt)                                             # candidate DG solution everywhere
+        self._update_and_reconstruct(dt, t0)
+        return count
+
+    def _one_volume_size(self, who):
+        # the FV patch update takes ONE volume size h (the reference's generated `time_step` has no cell size at all: SURVEY.md Appendix B): a grid with
+        # different cell sizes per axis would get a silently wrong update -- refused (as in oracle/limiter_numpy.py, which restates this glue)
+        s = self.s
+        if max(s.dx) - min(s.dx) > 1e-12 * max(s.dx):
+            raise ValueError("SubcellLimiter.%s: the FV patch update takes one volume size, the grid has dx = %s; use cells of equal size per axis" % (who, list(s.dx),))
+
+    def _compact(self, m):
+        """m: troubled flags, bool [n_cells] on the device -> self._cells (capacity-sized list, empty slots -1); returns the troubled count (0-dim)."""
+        torch = _torch()
+        cap = self.capacity
         # device-side compaction without a host-visible size: cell c goes to slot (number of troubled cells before it)
         rank = torch.cumsum(m, 0, dtype=torch.int64)
         count = rank[-1]
@@ -1181,23 +1205,32 @@ class SubcellLimiter:
         self._cells[cap] = -1
         self.overflow |= count > cap                           # sticky until check() has reported it
         self._post_overflow()
-        cells = self._cells
+        return count
+
+    def _project(self, m, u, t):
+        """The FV patches of the compacted cells from the state u at time t: flag / subcell-layer exchange on a sharded grid, ghost layers of
+        the domain faces, projection."""
+        torch = _torch()
+        s = self.s
         ghosts = None
         if self.hx_layer is not None:                          # every rank takes part, troubled cells or not
             nc3 = s.nc + [1] * (3 - s.dim)
             if self.exchange_events is not None:
                 e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
                 e0.record(torch.cuda.current_stream(s.dev))
-            ghosts = self._exchange_subcell_layers(m.to(torch.float64).reshape(nc3))
+            ghosts = self._exchange_subcell_layers(m.to(torch.float64).reshape(nc3), u)
             if self.exchange_events is not None:
                 e1.record(torch.cuda.current_stream(s.dev))
                 self.exchange_events.append((e0, e1))
-        ghosts = self._boundary_layers(ghosts)
-        patches = self._patches
-        check(s.lib.exa_dg_project_patches_ghost(s._plan, C.c_void_p(s.u.data_ptr()), C.c_void_p(cells.data_ptr()), cap,
-                                                 C.c_void_p(patches.data_ptr()), ghosts, _stream_ptr()))
-        t0 = s.time
-        s.step(dt)                                             # candidate DG solution everywhere
+        ghosts = self._boundary_layers(ghosts, u, t)
+        check(s.lib.exa_dg_project_patches_ghost(s._plan, C.c_void_p(u.data_ptr()), C.c_void_p(self._cells.data_ptr()), self.capacity,
+                                                 C.c_void_p(self._patches.data_ptr()), ghosts, _stream_ptr()))
+
+    def _update_and_reconstruct(self, dt, t0):
+        """FV update of the patches over [t0, t0 + dt] and their reconstruction into the solver's u."""
+        torch = _torch()
+        s = self.s
+        cells, patches, cap = self._cells, self._patches, self.capacity
         if self._xt:
             # centre of the patch in slot k = centre of its DG cell (device ops on the compacted list; unused slots: any value)
             c = cells[:cap].clamp(min=0)
@@ -1210,7 +1243,139 @@ class SubcellLimiter:
             self._fv.time_step(patches.reshape(-1), dt, s.dx[0] / self.Ns, slot=cells)
         check(s.lib.exa_dg_reconstruct_patches(s._plan, C.c_void_p(patches.data_ptr()), C.c_void_p(cells.data_ptr()), cap,
                                                C.c_void_p(s.u.data_ptr()), _stream_ptr()))
+
+    # -- a-posteriori (MOOD) limiting --------------------------------------------------------------
+    def _mood_setup(self):
+        """Buffers of the a-posteriori step, allocated once: u_old (a second copy of u: DOUBLES the memory of the degrees of freedom),
+        bounds[cell][4], the mask bytes, and on a sharded grid the exchange of the boundary layers' bounds."""
+        torch = _torch()
+        s = self.s
+        if s._one_kernel or s._fused:
+            raise ValueError("SubcellLimiter: the a-posteriori step needs the two-kernel solver step (u^n and the candidate in separate arrays, "
+                             "no pending corrector); construct the solver with one_kernel_step=False%s"
+                             % (", fused_single_stage=False" if s._fused else ""))
+        if getattr(self, "_u_old", None) is not None:
+            return
+        need = s._u.numel() * 8
+        free = torch.cuda.mem_get_info(s.dev)[0]
+        if need > free:
+            raise MemoryError("SubcellLimiter: the a-posteriori step keeps u^n beside the candidate: %.1f GB more, %.1f GB of device memory "
+                              "are free" % (need / 1e9, free / 1e9))
+        ncell = int(np.prod(s.nc))
+        self._bounds = torch.zeros((ncell, 4), dtype=torch.float64, device=s.dev)
+        self._mask = torch.zeros(tuple(s.nc), dtype=torch.bool, device=s.dev)
+        self.hx_bounds = None
+        if s.halo is not None:
+            self.hx_bounds = HaloExchange(s.part, s.nc, 4, s.dev, stage_through_host=s.halo.stage)
+        kinds = [0] * 6                                        # include/exahype_hip.h EXA_LIM_FACE_*
+        for d in range(s.dim):
+            for side in range(2):
+                if (d, side) in self._bc_layers:
+                    kinds[d * 2 + side] = 2
+                elif s.halo is not None and s.part.partitioned(d):
+                    kinds[d * 2 + side] = 1
+        self._face_kind = (C.c_int * 6)(*kinds)
+        self._u_old = torch.empty_like(s._u)
+
+    def _snapshot(self, u, u_old):
+        """bounds of u (and its copy into u_old, unless None); on a sharded grid the neighbours' boundary-layer bounds are exchanged."""
+        s = self.s
+        check(s.lib.exa_lim_snapshot(s._plan, C.c_void_p(u.data_ptr()), C.c_void_p(u_old.data_ptr()) if u_old is not None else None,
+                                     C.c_void_p(self._bounds.data_ptr()), _stream_ptr()))
+        hx = self.hx_bounds
+        if hx is not None:
+            nc3 = s.nc + [1] * (3 - s.dim)
+            b = self._bounds.reshape(nc3 + [4])
+            for d in range(s.dim):
+                if s.part.partitioned(d):
+                    hx.send[d * 2 + 0].copy_(b.select(d, 0).reshape(-1, 4))
+                    hx.send[d * 2 + 1].copy_(b.select(d, nc3[d] - 1).reshape(-1, 4))
+            hx.start()
+            hx.finish()
+
+    def _detect(self, u, d0, eps, floor):
+        """mask (bool [nc..], device) of the candidate u against the bounds of the last _snapshot"""
+        s = self.s
+        ghosts = self.hx_bounds.ghost_ptrs() if self.hx_bounds is not None else None
+        check(s.lib.exa_lim_detect(s._plan, C.c_void_p(u.data_ptr()), C.c_void_p(self._bounds.data_ptr()), ghosts, self._face_kind,
+                                   float(d0), float(eps), float(floor), C.c_void_p(self._mask.data_ptr()), _stream_ptr()))
+        return self._mask
+
+    def detect_candidate(self, u_old, d0=1e-4, eps=1e-3, floor=1e-12):
+        """The a-posteriori detector alone: bounds from the old state u_old (array like the solver's u), then the troubled mask of the solver's
+        current u as the candidate (exa_lim_snapshot without the copy + exa_lim_detect).  Returns a bool tensor [nc0, nc1, (nc2)] on the
+        device (the limiter's own buffer: clone it to keep it across calls)."""
+        torch = _torch()
+        s = self.s
+        self._mood_setup()
+        old = torch.as_tensor(u_old, dtype=torch.float64).to(s.dev).reshape(s._u.shape).contiguous()
+        self._snapshot(old, None)
+        return self._detect(s.u, d0, eps, floor)
+
+    def step_a_posteriori(self, dt, d0=1e-4, eps=1e-3, floor=1e-12):
+        """One limited step with the troubled cells found AFTER the DG step (MOOD).  u^n is kept (exa_lim_snapshot: copy + per-cell bounds of
+        density and energy in one pass), the solver's step gives the candidate everywhere, exa_lim_detect marks the cells whose candidate
+        is not finite, not positive (rho, p <= floor) or leaves the relaxed range delta = max(d0, eps (hi - lo)) of u^n over the face
+        neighbourhood, and those cells take the FV patch update of the projected u^n (neighbour layers, ghost layers and Dirichlet data of
+        the step's START) instead.  Whatever the candidate holds in a troubled cell -- NaN included -- is overwritten.
+
+        Costs a second array of the size of u (allocated at the first call; MemoryError if it does not fit) and two passes over u.
+        Nothing in here waits for the GPU; same return value, capacity / overflow / check() contract as step().  Not for the one-kernel
+        and the fused single-stage solver modes (ValueError)."""
+        s = self.s
+        self._one_volume_size("step_a_posteriori")
+        self._mood_setup()
+        self.check()
+        t0 = s.time
+        self._snapshot(s.u, self._u_old)
+        s.step(dt)                                             # candidate DG solution everywhere
+        m = self._detect(s.u, d0, eps, floor).reshape(-1)
+        count = self._compact(m)
+        self._project(m, self._u_old, t0)
+        self._update_and_reconstruct(dt, t0)
         return count
+
+    def run(self, t_end, cfl=0.4, max_steps=1000000, d0=1e-4, eps=1e-3, floor=1e-12, monitor=None, track=False):
+        """Advance the solver until its `time` reaches t_end with a-posteriori limited steps and the CFL step of AderDgSolver.run,
+        dt = cfl * min(dx) / ((2p+1) * d * lambda_max) (reduced over the ranks of a partition).  lambda_max of every step is scanned on the
+        LIMITED u (the scan fused into stage B would see the candidate, which may hold NaN in cells replaced afterwards).  Returns the
+        number of steps; ends with check(wait=True), so a step past the capacity raises.
+
+        monitor(limiter, step, count): called after every step (count: 0-dim device tensor).
+        track=True: self.stats = {"min_rho", "min_p", "max_troubled", "finite"} as 0-dim device tensors, running over every step's
+        result (torch passes over u: for tests and examples; reading them is the only synchronisation)."""
+        torch = _torch()
+        s = self.s
+        self._mood_setup()
+        steps = 0
+        if track:
+            self.stats = {"min_rho": torch.full((), float("inf"), dtype=torch.float64, device=s.dev),
+                          "min_p": torch.full((), float("inf"), dtype=torch.float64, device=s.dev),
+                          "max_troubled": torch.zeros((), dtype=torch.int64, device=s.dev),
+                          "finite": torch.ones((), dtype=torch.bool, device=s.dev)}
+        while s.time < t_end * (1 - 1e-14) and steps < max_steps:
+            lam = s.max_eigenvalue()
+            if s.boundary:
+                lam = s.boundary_eigenvalue(lam)
+            if s.part is not None and s.part.world > 1:
+                import torch.distributed as dist
+                dist.all_reduce(lam, op=dist.ReduceOp.MAX)
+            dt = _cfl_step(float(lam[0]), cfl * min(s.dx) / ((2 * s.N - 1) * s.dim), t_end - s.time, "SubcellLimiter.run")
+            count = self.step_a_posteriori(dt, d0, eps, floor)
+            if track:
+                u = s.u
+                st = self.stats
+                rho = u[..., 0]
+                ke = sum(u[..., 1 + a] ** 2 for a in range(min(3, s.nv - 2)))
+                st["min_rho"] = torch.minimum(st["min_rho"], rho.min())
+                st["min_p"] = torch.minimum(st["min_p"], (0.4 * (u[..., s.nv - 1] - 0.5 * ke / rho)).min())
+                st["max_troubled"] = torch.maximum(st["max_troubled"], count)
+                st["finite"] = st["finite"] & torch.isfinite(u).all()
+            if monitor is not None:
+                monitor(self, steps, count)
+            steps += 1
+        self.check(wait=True)
+        return steps
 
     def download(self):
         """The solver's u on the host -- after a WAITING check(): a result in which some troubled cells kept the unlimited DG solution is

@@ -272,6 +272,27 @@ int exa_lim_face_layers(exa_dg_plan* plan, const double* u_dev, int d, int side,
                         void* stream);
 int exa_dg_project_patches_ghost(exa_dg_plan* plan, const double* u_dev, const long* cells_dev, long n, double* patch_dev,
                                  const double* const* ghost_layers_dev, void* stream);
+/* A-posteriori (MOOD) troubled-cell detection for the limiter: the DG candidate of a step is checked AFTER the step against the
+ * state it started from, and the troubled cells are redone with the FV patch update from that state.  Euler variable layout:
+ * density first, energy last, min(3, n_vars - 2) momenta behind the density, gamma = 1.4.  Both are one pass over u.
+ * exa_lim_snapshot: copies u_dev (u^n) to u_old_dev (may be NULL: bounds only; must not be u_dev) and writes
+ * bounds_dev[cell][4] = min rho, max rho, min E, max E over the cell's nodes.
+ * exa_lim_detect: mask_dev[cell] (one byte per cell) = 1 if the candidate u_cand_dev is troubled in that cell, else 0:
+ *   (a) a value at a node is not finite, or rho <= floor or p <= floor at a node, p = 0.4 (E - |m|^2 / (2 rho)) (a NaN counts as troubled);
+ *   (b) relaxed discrete maximum principle on rho and on E: with lo / hi the minimum / maximum of bounds_dev over the cell and its
+ *       2*dim face neighbours and delta = max(d0, eps (hi - lo)), the candidate's nodal maximum exceeds hi + delta or its nodal
+ *       minimum falls below lo - delta.
+ * face_kind[d*2+side] (host, 2*dim entries, NULL = all periodic) says what lies across the block face (d, side):
+ * EXA_LIM_FACE_PERIODIC the periodic wrap inside the block; EXA_LIM_FACE_GHOST the neighbour block, whose boundary layer's bounds
+ * are in ghost_bounds_dev[d*2+side][transverse cell][4] (transverse cells lexicographic over the other axes, the last fastest);
+ * EXA_LIM_FACE_NONE a domain face with a boundary condition: no neighbour, the cell's own bounds.  ghost_bounds_dev may be NULL
+ * if no face is EXA_LIM_FACE_GHOST.  min / max are exact: the mask does not depend on the order of the reductions. */
+#define EXA_LIM_FACE_PERIODIC 0
+#define EXA_LIM_FACE_GHOST 1
+#define EXA_LIM_FACE_NONE 2
+int exa_lim_snapshot(exa_dg_plan* plan, const double* u_dev, double* u_old_dev, double* bounds_dev, void* stream);
+int exa_lim_detect(exa_dg_plan* plan, const double* u_cand_dev, const double* bounds_dev, const double* const* ghost_bounds_dev,
+                   const int* face_kind, double d0, double eps, double floor, unsigned char* mask_dev, void* stream);
 /* max over all cells/nodes/directions of maxEigenvalue (for a CFL time step);
  * result is written to *lambda_dev (one double, device). */
 int exa_dg_max_eigenvalue(exa_dg_plan* plan, const double* u_dev, double* lambda_dev, void* stream);
