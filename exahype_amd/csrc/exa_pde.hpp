@@ -99,7 +99,8 @@ template <class PDE> __device__ inline void dg_ncp(const double* q, const double
 
 // 1/x from v_rcp_f64 + EXA_RCP_NR Newton steps.  Measured on MI355X against the IEEE quotient
 // (scripts/rcp_accuracy.hip, 4M values): bare v_rcp_f64 2.6e8 ulp, one step <= 11 ulp (2.5e-15 relative), two
-// steps exact.  One step is the default: used by the ADER-DG kernels only (tolerance 1e-10; 2 % of stage A);
+// steps exact.  One step is the default: used by the ADER-DG kernels (2 % of stage A) and, through Euler::fv_aux, by the
+// plane-streaming FV kernel in corrected mode (held to the rounding bound these 11 ulp imply: tests/test_fv_kernels_hp.py);
 // the FV faithful kernel keeps the correctly rounded division the reference's CPU build performs.
 #ifndef EXA_RCP_NR
 #define EXA_RCP_NR 1
@@ -273,7 +274,7 @@ struct Euler {
     }
     // Per-volume scalars for the FV patch kernels (corrected Rusanov): every volume's flux and eigenvalue are needed by
     // its own update and by its 2*dim neighbours', so 1/rho, p and the sound speed are computed ONCE per volume (fast
-    // reciprocal / square root: <= 1e-15 relative, tolerance 1e-10) and kept beside the state.
+    // reciprocal / square root: <= 11 ulp / <= 1 ulp, which the tests' rounding bound accounts for) and kept beside the state.
     static constexpr int NFVAUX = 3;
     __device__ static inline void fv_aux(const double* q, double* a) {
         const double irho = fast_rcp(q[0]);

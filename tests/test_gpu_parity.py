@@ -108,6 +108,10 @@ def test_fv_faithful_and_corrected_vs_oracle_euler(exa, orc, dim, P, H, n_aux, n
     got = np.ascontiguousarray(Q.copy()); k.time_step(got, 0.01, 0.1)
     want = orc.fv_corrected(Q, 0.01, 0.1, dim, P, H, 5, n_aux, n_patches, orc.PDE_EULER)
     assert rel_err(got, want) < TOL
+    # ... and, beside it, element by element within the rounding bound of the long-double reference (tests/test_fv_kernels_hp.py)
+    from tests import fv_cases as K
+    row = (None, dim, P, H, 5, n_aux, n_patches, K.E, "inplace")
+    K.assert_within_bound(got, Q, 0.01, 0.1, dim, P, H, 5, n_aux, K.E, K.primitives(row), "parity %dd P=%d H=%d aux=%d" % (dim, P, H, n_aux))
 
 
 def test_fv_device_resident_and_empty(exa, orc):

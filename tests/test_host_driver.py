@@ -250,7 +250,9 @@ def _grid_state(grid, P, V, seed, dim):
 def test_grid_step_equals_halo_fill_plus_patch_update(dim, grid, P, H, n_aux, mode, dirichlet):
     """exa_fv_grid_step_device (halo-less arrays; the states beyond a patch face taken from the neighbours inside the launch) is BIT-equal to
     the two-pass form it replaces -- halo fill of an array with halo, then the in-place `time_step` -- for every kernel variant the dispatch
-    knows, periodic and with prescribed boundary states, over several steps (so the array swap is exercised)."""
+    knows, periodic and with prescribed boundary states, over several steps (so the array swap is exercised).  Two forms that share an arithmetic
+    error agree bit for bit: the arithmetic itself (and the fused CFL scalar) is checked against the long-double reference in
+    tests/test_fv_kernels_hp.py."""
     from exahype_amd import solvers as exa
     V = 5 + n_aux
     pde = exa.PDE_EULER_REF2D if (dim == 2 and mode == "faithful") else exa.PDE_EULER

@@ -123,3 +123,11 @@ def log_limiter_measurement(kind, **fields):
     if os.environ.get("EXA_LIM_ERR_LOG"):
         with open(os.environ["EXA_LIM_ERR_LOG"], "a") as f:
             f.write(json.dumps(dict(kind=kind, test=os.environ.get("PYTEST_CURRENT_TEST", ""), **fields)) + "\n")
+
+
+def log_fv_measurement(**fields):
+    """Measurement aid of tests/test_fv_kernels_hp.py, like EXA_LIM_ERR_LOG above: with EXA_FV_ERR_LOG=<file> every comparison appends one JSON line
+    (row, family, entry, the largest error / bound ratio it saw)."""
+    if os.environ.get("EXA_FV_ERR_LOG"):
+        with open(os.environ["EXA_FV_ERR_LOG"], "a") as f:
+            f.write(json.dumps(dict(test=os.environ.get("PYTEST_CURRENT_TEST", ""), **fields)) + "\n")
