@@ -62,6 +62,9 @@ SIGNATURES = {
     "exa_dg_reconstruct_patches": (C.c_int, [_vp, _vp, _vp, C.c_long, _vp, _vp]),
     "exa_lim_snapshot": (C.c_int, [_vp, _vp, _vp, _vp, _vp]),
     "exa_lim_detect": (C.c_int, [_vp, _vp, _vp, C.POINTER(_vp), C.POINTER(C.c_int), C.c_double, C.c_double, C.c_double, _vp, _vp]),
+    "exa_lim_face_flux_count": (C.c_long, [_vp]),
+    "exa_lim_face_flux": (C.c_int, [_vp, _vp, _vp, C.c_long, _vp, _vp]),
+    "exa_lim_interface_correct": (C.c_int, [_vp, _vp, _vp, _vp, C.c_long, _vp, C.POINTER(C.c_int), _vp, C.c_double, _dp, _vp]),
     "exa_dg_max_eigenvalue": (C.c_int, [_vp, _vp, _vp, _vp]),
     "exa_dg_has_fused_step": (C.c_int, [_vp]),
     "exa_dg_step_fused": (C.c_int, [_vp, _vp, _vp, C.c_double, _dp, _vp]),

@@ -687,6 +687,59 @@ int exa_lim_detect(exa_dg_plan* p, const double* u_cand_dev, const double* bound
     return limiter_detect(p->dim, p->N, p->nv, p->nc, u_cand_dev, bounds_dev, &gb, face_kind, d0, eps, floor, mask_dev, (hipStream_t)stream);
 }
 
+// term sets the conservative interface is built for: the built-in Euler (5 variables) and advection (1 variable) sets
+static int lim_conservative_pde(const exa_dg_plan* p, const char* who) {
+    if (exa_pde_flags(p->pde) & (EXA_PDE_FLAG_XT | EXA_PDE_FLAG_NCP)) {
+        set_error("%s: term set %d carries position- / time-dependent terms or a non-conservative product; the conservative interface is built for the built-in Euler and advection sets", who, p->pde);
+        return EXA_ERR_INVALID;
+    }
+    if (!((p->pde == 1 && p->nv == 5) || (p->pde == 2 && p->nv == 1))) {
+        set_error("%s: term set %d with %d variables; the conservative interface is built for the built-in Euler (pde 1, 5 variables) and advection (pde 2, 1 variable) sets, "
+                  "not for registered ones", who, p->pde, p->nv);
+        return EXA_ERR_INVALID;
+    }
+    return EXA_OK;
+}
+
+long exa_lim_face_flux_count(const exa_dg_plan* p) { return p ? 2L * p->dim * p->nv * lpow(p->N, p->dim - 1) : 0; }
+
+int exa_lim_face_flux(exa_dg_plan* p, const double* patch_dev, const long* cells_dev, long n, double* fvflux_dev, void* stream) {
+    if (!p || n < 0 || (n > 0 && (!patch_dev || !cells_dev || !fvflux_dev))) { set_error("exa_lim_face_flux: bad argument (NULL plan or array, or n < 0)"); return EXA_ERR_INVALID; }
+    int rc = use_device(p->device);
+    if (rc) return rc;
+    rc = lim_conservative_pde(p, "exa_lim_face_flux");
+    if (rc) return rc;
+    rc = lim_tables(p);
+    if (rc) return rc;
+    const int Ns = 2 * p->N - 1;
+    return limiter_face_flux(p->dim, p->N, p->pde, patch_dev, cells_dev, n, fvflux_dev, static_cast<const double*>(p->ops.lim) + (size_t)p->N * Ns,
+                             (hipStream_t)stream) == 0 ? EXA_OK : EXA_ERR_HIP;
+}
+
+int exa_lim_interface_correct(exa_dg_plan* p, double* u_dev, const double* trace_dev, const long* cells_dev, long n, const unsigned char* mask_dev,
+                              const int* face_kind, const double* fvflux_dev, double dt, const double* dx, void* stream) {
+    if (!p || !u_dev || !trace_dev || !mask_dev || !dx || n < 0 || (n > 0 && (!cells_dev || !fvflux_dev))) {
+        set_error("exa_lim_interface_correct: bad argument (NULL plan or array, or n < 0)");
+        return EXA_ERR_INVALID;
+    }
+    int rc = use_device(p->device);
+    if (rc) return rc;
+    rc = lim_conservative_pde(p, "exa_lim_interface_correct");
+    if (rc) return rc;
+    for (int f = 0; f < 2 * p->dim; f++) {
+        const int kind = face_kind ? face_kind[f] : EXA_LIM_FACE_PERIODIC;
+        if (kind == EXA_LIM_FACE_GHOST) {
+            set_error("exa_lim_interface_correct: face %d is EXA_LIM_FACE_GHOST; the exchange of face fluxes between blocks is not built", f);
+            return EXA_ERR_INVALID;
+        }
+        if (kind != EXA_LIM_FACE_PERIODIC && kind != EXA_LIM_FACE_NONE) { set_error("exa_lim_interface_correct: face_kind[%d] = %d", f, kind); return EXA_ERR_INVALID; }
+    }
+    for (int a = 0; a < p->dim; a++)
+        if (!(dx[a] > 0.0)) { set_error("exa_lim_interface_correct: dx[%d] must be positive", a); return EXA_ERR_INVALID; }
+    return limiter_interface_correct(p->dim, p->N, p->pde, p->nc, u_dev, trace_dev, cells_dev, n, mask_dev, face_kind, fvflux_dev, dt, dx,
+                                     p->ops.w, p->ops.phiL, p->ops.phiR, (hipStream_t)stream) == 0 ? EXA_OK : EXA_ERR_HIP;
+}
+
 int exa_dg_max_eigenvalue(exa_dg_plan* p, const double* u_dev, double* lambda_dev, void* stream) {
     if (!p || !u_dev || !lambda_dev) { set_error("exa_dg_max_eigenvalue: NULL argument"); return EXA_ERR_INVALID; }
     int rc = use_device(p->device);

@@ -35,6 +35,12 @@ int limiter_reconstruct(int dim, int N, int Ns, int nv, const double* patch, con
 int limiter_snapshot(int dim, int N, int nv, long ncells, const double* u, double* u_old, double* bounds, hipStream_t s);
 int limiter_detect(int dim, int N, int nv, const long* nc, const double* u, const double* bounds, const LimGhosts* ghosts, const int* kinds,
                    double d0, double eps, double floor, unsigned char* mask, hipStream_t s);
+// conservative DG / FV interface (pde: 1 Euler, 2 advection): FV face fluxes of the listed patches at the DG face nodes, fvflux[slot][d*2+side][var][node];
+// their lift into the untroubled (mask == 0) face neighbours of the listed cells, one launch per (axis, side)
+int limiter_face_flux(int dim, int N, int pde, const double* patch, const long* cells, long n, double* fvflux, const double* Rdev, hipStream_t s);
+int limiter_interface_correct(int dim, int N, int pde, const long* nc, double* u, const double* trace, const long* cells, long n,
+                              const unsigned char* mask, const int* kinds, const double* fvflux, double dt, const double* dx,
+                              const double* w, const double* phiL, const double* phiR, hipStream_t s);
 
 struct StageBBox {
     long nc[3], lo[3], nb[3];

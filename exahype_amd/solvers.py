@@ -1162,16 +1162,21 @@ class SubcellLimiter:
         hl.finish()
         return hl.ghost_ptrs()
 
-    def step(self, dt, mask):
+    def step(self, dt, mask, conservative=False):
         """One limited step.  mask: troubled flags [nc0, nc1, (nc2)] (CUDA bool tensor stays on the device; numpy is
         uploaded).  Nothing in here waits for the GPU: the troubled cells are compacted on the device into a
         capacity-sized list (empty slots = -1) that the projection, the FV patch update and the reconstruction
         skip, and one FV plan of `capacity` patches serves every step.  Returns the number of troubled cells as a
         0-dim CUDA tensor (int(...) of it synchronises; the kernels do not need it).  More troubled cells than
-        `capacity` cannot be served: `self.overflow` (0-dim CUDA bool) says so -- see check()."""
+        `capacity` cannot be served: `self.overflow` (0-dim CUDA bool) says so -- see check().
+
+        conservative=True: one round of the conservative DG / FV interface with the given mask -- the untroubled face neighbours of the
+        troubled cells trade the DG face flux for the FV one (exa_lim_face_flux / exa_lim_interface_correct; see step_a_posteriori)."""
         torch = _torch()
         s = self.s
         self._one_volume_size("step")
+        if conservative:
+            self._conservative_setup("step")
         self.check()                                           # a COMPLETED earlier step past the capacity raises here (no synchronisation)
         if isinstance(mask, torch.Tensor):
             m = mask.to(device=s.dev, dtype=torch.bool)
@@ -1180,9 +1185,13 @@ class SubcellLimiter:
         m = m.reshape(-1)
         count = self._compact(m)
         self._project(m, s.u, s.time)
+        if conservative:
+            self._face_flux()
         t0 = s.time
         s.step(dt)                                             # candidate DG solution everywhere
         self._update_and_reconstruct(dt, t0)
+        if conservative:
+            self._interface_correct(m.contiguous(), dt)
         return count
 
     def _one_volume_size(self, who):
@@ -1244,6 +1253,54 @@ class SubcellLimiter:
         check(s.lib.exa_dg_reconstruct_patches(s._plan, C.c_void_p(patches.data_ptr()), C.c_void_p(cells.data_ptr()), cap,
                                                C.c_void_p(s.u.data_ptr()), _stream_ptr()))
 
+    # -- conservative DG / FV interface --------------------------------------------------------------
+    def _face_kinds(self):
+        """include/exahype_hip.h EXA_LIM_FACE_* of the block's 2*dim faces"""
+        s = self.s
+        kinds = [0] * 6
+        for d in range(s.dim):
+            for side in range(2):
+                if (d, side) in self._bc_layers:
+                    kinds[d * 2 + side] = 2
+                elif s.halo is not None and s.part.partitioned(d):
+                    kinds[d * 2 + side] = 1
+        return (C.c_int * 6)(*kinds)
+
+    def _conservative_setup(self, who):
+        """What the conservative interface needs, checked and allocated once: the FV face fluxes of the patches at the DG face nodes
+        [capacity][2 dim][n_vars][N^(dim-1)] and the cumulative mask of a step."""
+        torch = _torch()
+        s = self.s
+        if getattr(self, "_fvflux", None) is not None:
+            return
+        if s.halo is not None:
+            raise ValueError("SubcellLimiter.%s(conservative=True): the grid is partitioned; the exchange of the FV face fluxes between the "
+                             "blocks of a sharded grid is out of scope of the conservative interface (run it on one block)" % who)
+        if s._one_kernel or s._fused:
+            raise ValueError("SubcellLimiter.%s(conservative=True): needs the two-kernel solver step (the face traces of the step in memory, no "
+                             "pending corrector); construct the solver with one_kernel_step=False%s" % (who, ", fused_single_stage=False" if s._fused else ""))
+        flags = s.lib.exa_pde_flags(int(s.pde))
+        if flags & 3 or (int(s.pde), s.nv) not in ((PDE_EULER, 5), (PDE_ADVECTION, 1)):
+            raise ValueError("SubcellLimiter.%s(conservative=True): built for the built-in Euler (5 variables) and advection (1 variable) term sets; "
+                             "term set %d with %d variables%s is not served" % (who, int(s.pde), s.nv, " (position / time dependent terms or a "
+                                                                                "non-conservative product)" if flags & 3 else ""))
+        self._cons_kind = self._face_kinds()
+        self._mask_cum = torch.zeros(tuple(s.nc), dtype=torch.bool, device=s.dev)
+        self._fvflux = torch.zeros((self.capacity, s.lib.exa_lim_face_flux_count(s._plan)), dtype=torch.float64, device=s.dev)
+
+    def _face_flux(self):
+        """FV face fluxes of the projected patches (before the in-place FV update overwrites their boundary layers)"""
+        s = self.s
+        check(s.lib.exa_lim_face_flux(s._plan, C.c_void_p(self._patches.data_ptr()), C.c_void_p(self._cells.data_ptr()), self.capacity,
+                                      C.c_void_p(self._fvflux.data_ptr()), _stream_ptr()))
+
+    def _interface_correct(self, mask, dt):
+        """The untroubled (mask == 0; bool tensor over the cells, device) face neighbours of the compacted cells trade F* for the FV face flux"""
+        s = self.s
+        check(s.lib.exa_lim_interface_correct(s._plan, C.c_void_p(s.u.data_ptr()), C.c_void_p(s.trace.data_ptr()), C.c_void_p(self._cells.data_ptr()),
+                                              self.capacity, C.c_void_p(mask.data_ptr()), self._cons_kind, C.c_void_p(self._fvflux.data_ptr()),
+                                              dt, darr(s.dx), _stream_ptr()))
+
     # -- a-posteriori (MOOD) limiting --------------------------------------------------------------
     def _mood_setup(self):
         """Buffers of the a-posteriori step, allocated once: u_old (a second copy of u: DOUBLES the memory of the degrees of freedom),
@@ -1267,14 +1324,7 @@ class SubcellLimiter:
         self.hx_bounds = None
         if s.halo is not None:
             self.hx_bounds = HaloExchange(s.part, s.nc, 4, s.dev, stage_through_host=s.halo.stage)
-        kinds = [0] * 6                                        # include/exahype_hip.h EXA_LIM_FACE_*
-        for d in range(s.dim):
-            for side in range(2):
-                if (d, side) in self._bc_layers:
-                    kinds[d * 2 + side] = 2
-                elif s.halo is not None and s.part.partitioned(d):
-                    kinds[d * 2 + side] = 1
-        self._face_kind = (C.c_int * 6)(*kinds)
+        self._face_kind = self._face_kinds()
         self._u_old = torch.empty_like(s._u)
 
     def _snapshot(self, u, u_old):
@@ -1312,7 +1362,7 @@ class SubcellLimiter:
         self._snapshot(old, None)
         return self._detect(s.u, d0, eps, floor)
 
-    def step_a_posteriori(self, dt, d0=1e-4, eps=1e-3, floor=1e-12):
+    def step_a_posteriori(self, dt, d0=1e-4, eps=1e-3, floor=1e-12, conservative=False, rounds=3):
         """One limited step with the troubled cells found AFTER the DG step (MOOD).  u^n is kept (exa_lim_snapshot: copy + per-cell bounds of
         density and energy in one pass), the solver's step gives the candidate everywhere, exa_lim_detect marks the cells whose candidate
         is not finite, not positive (rho, p <= floor) or leaves the relaxed range delta = max(d0, eps (hi - lo)) of u^n over the face
@@ -1321,10 +1371,21 @@ class SubcellLimiter:
 
         Costs a second array of the size of u (allocated at the first call; MemoryError if it does not fit) and two passes over u.
         Nothing in here waits for the GPU; same return value, capacity / overflow / check() contract as step().  Not for the one-kernel
-        and the fused single-stage solver modes (ValueError)."""
+        and the fused single-stage solver modes (ValueError).
+
+        conservative=True: the DG / FV interface is made conservative, in a fixed number of `rounds` (not data dependent: still no wait).
+        A round detects on the current u against the bounds of u^n, redoes the NEWLY troubled cells (not yet in the step's cumulative
+        mask, `self._mask_cum`) with the FV update of the projected u^n, and corrects their face neighbours outside the cumulative mask:
+        those replace the DG face flux F* of the common face by the FV flux of the troubled side (exa_lim_face_flux, lifted as the corrector
+        lifts it: exa_lim_interface_correct), so the neighbour's mean changes by what the troubled cell's mean changed, with the opposite
+        sign.  A corrected neighbour can leave the admissible states: the next round detects it.  The capacity holds per round; the return
+        value is the number of cells in the cumulative mask.  One block only (ValueError on a partitioned grid: the exchange of face fluxes
+        between blocks is out of scope), built-in Euler / advection term sets only."""
         s = self.s
         self._one_volume_size("step_a_posteriori")
         self._mood_setup()
+        if conservative:
+            return self._step_conservative(dt, d0, eps, floor, int(rounds))
         self.check()
         t0 = s.time
         self._snapshot(s.u, self._u_old)
@@ -1335,7 +1396,31 @@ class SubcellLimiter:
         self._update_and_reconstruct(dt, t0)
         return count
 
-    def run(self, t_end, cfl=0.4, max_steps=1000000, d0=1e-4, eps=1e-3, floor=1e-12, monitor=None, track=False):
+    def _step_conservative(self, dt, d0, eps, floor, rounds):
+        s = self.s
+        if rounds < 1:
+            raise ValueError("SubcellLimiter.step_a_posteriori: rounds must be >= 1")
+        self._conservative_setup("step_a_posteriori")
+        self.check()
+        t0 = s.time
+        self._snapshot(s.u, self._u_old)
+        s.step(dt)                                             # candidate DG solution everywhere; its traces stay intact for the rounds
+        cum = self._mask_cum
+        cum.zero_()
+        total = None
+        for _ in range(rounds):                                # (a round without new cells launches over -1 slots)
+            new = self._detect(s.u, d0, eps, floor) & ~cum
+            cum |= new
+            m = new.reshape(-1)
+            count = self._compact(m)                           # the capacity holds per round: earlier rounds' patches are done with
+            self._project(m, self._u_old, t0)
+            self._face_flux()
+            self._update_and_reconstruct(dt, t0)
+            self._interface_correct(cum, dt)
+            total = count if total is None else total + count
+        return total
+
+    def run(self, t_end, cfl=0.4, max_steps=1000000, d0=1e-4, eps=1e-3, floor=1e-12, monitor=None, track=False, conservative=False, rounds=3):
         """Advance the solver until its `time` reaches t_end with a-posteriori limited steps and the CFL step of AderDgSolver.run,
         dt = cfl * min(dx) / ((2p+1) * d * lambda_max) (reduced over the ranks of a partition).  lambda_max of every step is scanned on the
         LIMITED u (the scan fused into stage B would see the candidate, which may hold NaN in cells replaced afterwards).  Returns the
@@ -1343,16 +1428,23 @@ class SubcellLimiter:
 
         monitor(limiter, step, count): called after every step (count: 0-dim device tensor).
         track=True: self.stats = {"min_rho", "min_p", "max_troubled", "finite"} as 0-dim device tensors, running over every step's
-        result (torch passes over u: for tests and examples; reading them is the only synchronisation)."""
+        result (torch passes over u: for tests and examples; reading them is the only synchronisation).
+        conservative, rounds: see step_a_posteriori (lambda_max is scanned after the last round).  With track=True, stats then also holds
+        "unresolved": the number of cells one more detection after the last round would still mark, summed over the steps (one extra
+        detection pass per step)."""
         torch = _torch()
         s = self.s
         self._mood_setup()
+        if conservative:
+            self._conservative_setup("run")
         steps = 0
         if track:
             self.stats = {"min_rho": torch.full((), float("inf"), dtype=torch.float64, device=s.dev),
                           "min_p": torch.full((), float("inf"), dtype=torch.float64, device=s.dev),
                           "max_troubled": torch.zeros((), dtype=torch.int64, device=s.dev),
                           "finite": torch.ones((), dtype=torch.bool, device=s.dev)}
+            if conservative:
+                self.stats["unresolved"] = torch.zeros((), dtype=torch.int64, device=s.dev)
         while s.time < t_end * (1 - 1e-14) and steps < max_steps:
             lam = s.max_eigenvalue()
             if s.boundary:
@@ -1361,10 +1453,12 @@ class SubcellLimiter:
                 import torch.distributed as dist
                 dist.all_reduce(lam, op=dist.ReduceOp.MAX)
             dt = _cfl_step(float(lam[0]), cfl * min(s.dx) / ((2 * s.N - 1) * s.dim), t_end - s.time, "SubcellLimiter.run")
-            count = self.step_a_posteriori(dt, d0, eps, floor)
+            count = self.step_a_posteriori(dt, d0, eps, floor, conservative, rounds) if conservative else self.step_a_posteriori(dt, d0, eps, floor)
             if track:
                 u = s.u
                 st = self.stats
+                if conservative:
+                    st["unresolved"] = st["unresolved"] + (self._detect(u, d0, eps, floor) & ~self._mask_cum).sum()
                 rho = u[..., 0]
                 ke = sum(u[..., 1 + a] ** 2 for a in range(min(3, s.nv - 2)))
                 st["min_rho"] = torch.minimum(st["min_rho"], rho.min())

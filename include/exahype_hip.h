@@ -293,6 +293,26 @@ int exa_dg_project_patches_ghost(exa_dg_plan* plan, const double* u_dev, const l
 int exa_lim_snapshot(exa_dg_plan* plan, const double* u_dev, double* u_old_dev, double* bounds_dev, void* stream);
 int exa_lim_detect(exa_dg_plan* plan, const double* u_cand_dev, const double* bounds_dev, const double* const* ghost_bounds_dev,
                    const int* face_kind, double d0, double eps, double floor, unsigned char* mask_dev, void* stream);
+/* Conservative DG / FV interface for the a-posteriori limiter.  A troubled cell is redone with the FV patch update, its untroubled
+ * face neighbour keeps the DG corrector: on their common face the two used different fluxes.  Built-in Euler (5 variables) and advection
+ * (1 variable) term sets; EXA_PDE_FLAG_XT / EXA_PDE_FLAG_NCP and registered term sets return EXA_ERR_INVALID.  -1 slots are skipped.
+ * exa_lim_face_flux: BEFORE the in-place FV update of the patches (exa_fv_time_step_device overwrites their boundary layers): for each
+ *   listed patch and each of its 2*dim faces the corrected-mode Rusanov flux g = (f_d(Q-) + f_d(Q+)) / 2 - max(l_d(Q-), l_d(Q+)) (Q+ - Q-) / 2
+ *   between the boundary layer and the halo layer on the N_s^(dim-1) subfaces (Q-: the lower index along d), brought to the N^(dim-1) face
+ *   nodes with the reconstruction operator, (R x R) g, which keeps the face mean: fvflux_dev[slot][d*2+side][var][face node],
+ *   exa_lim_face_flux_count(plan) doubles per slot, the [var][node] order of one field of the trace array.
+ * exa_lim_interface_correct: AFTER exa_dg_reconstruct_patches, with the trace array of the step still intact: for every face (d, side) of a
+ *   listed cell T whose neighbour D across it has mask_dev[D] == 0 (the CUMULATIVE troubled mask of the step, T's own flag included), the DG
+ *   face flux F* = (F- + F+) / 2 - s (q+ - q-) / 2, s the largest eigenvalue over all nodes of the face, is recomputed as the Riemann /
+ *   corrector pass did, and D takes the corrector's lift of dF = fvflux - F*:  u_D -= dt/dx_d phiR_i / w_i dF (its upper face),
+ *   u_D += dt/dx_d phiL_i / w_i dF (its lower face) -- its mean changes by what T's mean changed, with the opposite sign.
+ *   face_kind as for exa_lim_detect: EXA_LIM_FACE_NONE faces of the block have no neighbour and are left alone, EXA_LIM_FACE_GHOST is
+ *   refused (the exchange of face fluxes between blocks is not built).  One launch per (axis, side): no atomics, deterministic. */
+long exa_lim_face_flux_count(const exa_dg_plan* plan);
+int exa_lim_face_flux(exa_dg_plan* plan, const double* patch_dev, const long* cells_dev, long n, double* fvflux_dev, void* stream);
+int exa_lim_interface_correct(exa_dg_plan* plan, double* u_dev, const double* trace_dev, const long* cells_dev, long n,
+                              const unsigned char* mask_dev, const int* face_kind, const double* fvflux_dev, double dt, const double* dx,
+                              void* stream);
 /* max over all cells/nodes/directions of maxEigenvalue (for a CFL time step);
  * result is written to *lambda_dev (one double, device). */
 int exa_dg_max_eigenvalue(exa_dg_plan* plan, const double* u_dev, double* lambda_dev, void* stream);
