@@ -60,6 +60,7 @@ SIGNATURES = {
     "exa_lim_face_layer_count": (C.c_long, [_vp, C.c_int]),
     "exa_lim_face_layers": (C.c_int, [_vp, _vp, C.c_int, C.c_int, _vp, _vp, _vp]),
     "exa_dg_reconstruct_patches": (C.c_int, [_vp, _vp, _vp, C.c_long, _vp, _vp]),
+    "exa_lim_bounds_count": (C.c_long, [_vp]),
     "exa_lim_snapshot": (C.c_int, [_vp, _vp, _vp, _vp, _vp]),
     "exa_lim_detect": (C.c_int, [_vp, _vp, _vp, C.POINTER(_vp), C.POINTER(C.c_int), C.c_double, C.c_double, C.c_double, _vp, _vp]),
     "exa_lim_face_flux_count": (C.c_long, [_vp]),

@@ -44,6 +44,10 @@ struct UserPde {
     int (*fv)(int, int, int, int, int, int, long, double*, double, double, const long*, void*, double*, const double*, double, const void*);
     int (*fvmax)(int, int, int, int, int, long, const double*, double*, void*, const double*, double, double);
     int (*ev)(int, long, int, const double*, double*, double*, void*, const double*, double);
+    // the term set's own a-posteriori detector (EXA_PDE_FLAG_ADMISSIBLE; lim_user.hip) and its watched-variable count
+    int k_dmp;
+    int (*lim_snap)(int, int, long, const double*, double*, double*, void*);
+    int (*lim_det)(int, int, const long*, const double*, const double*, const double* const*, const int*, double, double, double, unsigned char*, void*);
 };
 static std::vector<UserPde> g_user;
 
@@ -139,6 +143,17 @@ int exa_register_pde(const char* library_path, int* pde_id) {
     u.nv = nvf();
     int (*flf)() = (int (*)())dlsym(h, "exa_user_pde_flags");
     u.flags = flf ? flf() : 0;
+    if (u.flags & EXA_PDE_FLAG_ADMISSIBLE) {
+        int (*kf)() = (int (*)())dlsym(h, "exa_user_lim_k_dmp");
+        u.lim_snap = (decltype(u.lim_snap))dlsym(h, "exa_user_lim_snapshot");
+        u.lim_det = (decltype(u.lim_det))dlsym(h, "exa_user_lim_detect");
+        if (!kf || !u.lim_snap || !u.lim_det) {
+            dlclose(h);
+            set_error("%s carries an admissibility criterion but exports no exa_user_lim_snapshot / exa_user_lim_detect", library_path);
+            return EXA_ERR_INVALID;
+        }
+        u.k_dmp = kf();
+    }
     g_user.push_back(u);
     *pde_id = 100 + (int)g_user.size() - 1;
     return EXA_OK;
@@ -661,29 +676,48 @@ int exa_dg_reconstruct_patches(exa_dg_plan* p, const double* patch_dev, const lo
                                static_cast<const double*>(p->ops.lim) + (size_t)p->N * Ns, (hipStream_t)stream);
 }
 
+// the registered term set of the plan if it carries its own criterion (EXA_PDE_FLAG_ADMISSIBLE), else null
+static const UserPde* lim_user(const exa_dg_plan* p) {
+    if (p->pde < 100 || p->pde - 100 >= (int)g_user.size()) return nullptr;
+    const UserPde* u = &g_user[p->pde - 100];
+    return (u->flags & EXA_PDE_FLAG_ADMISSIBLE) ? u : nullptr;
+}
+
+long exa_lim_bounds_count(const exa_dg_plan* p) {
+    if (!p) return 0;
+    const UserPde* up = lim_user(p);
+    return up ? 2L * up->k_dmp : 4;
+}
+
 int exa_lim_snapshot(exa_dg_plan* p, const double* u_dev, double* u_old_dev, double* bounds_dev, void* stream) {
-    if (!p || !u_dev || !bounds_dev || u_dev == u_old_dev) { set_error("exa_lim_snapshot: bad argument (plan, u_dev or bounds_dev is NULL, or u_old_dev == u_dev)"); return EXA_ERR_INVALID; }
+    const bool no_bounds = p && u_dev && exa_lim_bounds_count(p) == 0;         // (nothing watched: bounds_dev is not touched)
+    if (!p || !u_dev || (!bounds_dev && !no_bounds) || u_dev == u_old_dev) { set_error("exa_lim_snapshot: bad argument (plan, u_dev or bounds_dev is NULL, or u_old_dev == u_dev)"); return EXA_ERR_INVALID; }
     int rc = use_device(p->device);
     if (rc) return rc;
+    if (const UserPde* up = lim_user(p)) return up->lim_snap(p->dim, p->N, p->ncells, u_dev, u_old_dev, bounds_dev, stream);
     return limiter_snapshot(p->dim, p->N, p->nv, p->ncells, u_dev, u_old_dev, bounds_dev, (hipStream_t)stream);
 }
 
 int exa_lim_detect(exa_dg_plan* p, const double* u_cand_dev, const double* bounds_dev, const double* const* ghost_bounds_dev,
                    const int* face_kind, double d0, double eps, double floor, unsigned char* mask_dev, void* stream) {
-    if (!p || !u_cand_dev || !bounds_dev || !mask_dev) { set_error("exa_lim_detect: NULL argument"); return EXA_ERR_INVALID; }
+    const bool no_bounds = p && u_cand_dev && mask_dev && exa_lim_bounds_count(p) == 0;
+    if (!p || !u_cand_dev || (!bounds_dev && !no_bounds) || !mask_dev) { set_error("exa_lim_detect: NULL argument"); return EXA_ERR_INVALID; }
     int rc = use_device(p->device);
     if (rc) return rc;
-    if (p->nv < 2) { set_error("exa_lim_detect: needs a density and an energy (n_vars >= 2), the plan has %d", p->nv); return EXA_ERR_INVALID; }
+    const UserPde* up = lim_user(p);
+    if (!up && p->nv < 2) { set_error("exa_lim_detect: needs a density and an energy (n_vars >= 2), the plan has %d", p->nv); return EXA_ERR_INVALID; }
     if (!(d0 >= 0.0) || !(eps >= 0.0) || floor != floor) { set_error("exa_lim_detect: d0 and eps must be >= 0 and floor a number"); return EXA_ERR_INVALID; }
     LimGhosts gb{};
     for (int f = 0; f < 2 * p->dim; f++) {
         const int kind = face_kind ? face_kind[f] : EXA_LIM_FACE_PERIODIC;
         if (kind < EXA_LIM_FACE_PERIODIC || kind > EXA_LIM_FACE_NONE) { set_error("exa_lim_detect: face_kind[%d] = %d", f, kind); return EXA_ERR_INVALID; }
         if (kind == EXA_LIM_FACE_GHOST) {
+            if (no_bounds) continue;                                                   // (nothing watched: no neighbourhood)
             if (!ghost_bounds_dev || !ghost_bounds_dev[f]) { set_error("exa_lim_detect: face %d is EXA_LIM_FACE_GHOST without ghost bounds", f); return EXA_ERR_INVALID; }
             gb.layer[f] = ghost_bounds_dev[f];
         }
     }
+    if (up) return up->lim_det(p->dim, p->N, p->nc, u_cand_dev, bounds_dev, gb.layer, face_kind, d0, eps, floor, mask_dev, stream);
     return limiter_detect(p->dim, p->N, p->nv, p->nc, u_cand_dev, bounds_dev, &gb, face_kind, d0, eps, floor, mask_dev, (hipStream_t)stream);
 }
 

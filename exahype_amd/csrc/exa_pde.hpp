@@ -74,6 +74,12 @@ template <class PDE> __device__ inline void fv_ncp(const double* q, const double
     if constexpr (pde_has_xt<PDE>::value) PDE::ncp_xt(q, dq, x, t, d, out);
     else PDE::ncp(q, dq, d, out);
 }
+// Optional: `static constexpr bool HAS_ADMISSIBLE = true` with K_ADM, K_DMP, DMP_VAR[], dmp_var(k) and admissible(q, g) -- what the
+// a-posteriori subcell limiter's detector checks for this term set (exa_lim_detect.hpp): a node is admissible iff every g[k] > floor
+// (K_ADM values, IEEE arithmetic), and the relaxed discrete maximum principle watches the K_DMP variables DMP_VAR[].  A term set
+// without it is checked in the Euler layout (density first, energy last).  pde_codegen.SympyPDE(admissible=..., dmp=...) generates one.
+template <class P, class = void> struct pde_has_admissible : std::false_type {};
+template <class P> struct pde_has_admissible<P, std::void_t<decltype(P::HAS_ADMISSIBLE)>> : std::bool_constant<P::HAS_ADMISSIBLE> {};
 
 // The same terms for the ADER-DG kernels (tolerance 1e-10): generated term sets carry `_fast` twins whose reciprocals / square roots use the
 // fast sequences below (pde_codegen.py); a term set without them is evaluated as it is.

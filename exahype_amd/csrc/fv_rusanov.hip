@@ -1370,7 +1370,9 @@ static int fv_mode(int mode, int P, int H, int m, int V, long n_patches, double*
 // user-PDE side library: the same fused kernel instantiated for exa::UserPDE
 extern "C" int exa_user_nv() { return exa::UserPDE::NV; }
 // bit 0: the terms depend on position / time (HAS_XT), bit 1: the term set carries a non-conservative product (HAS_NCP)
-extern "C" int exa_user_pde_flags() { return (exa::pde_has_xt<exa::UserPDE>::value ? 1 : 0) | (exa::pde_has_ncp<exa::UserPDE>::value ? 2 : 0); }
+extern "C" int exa_user_pde_flags() {
+    return (exa::pde_has_xt<exa::UserPDE>::value ? 1 : 0) | (exa::pde_has_ncp<exa::UserPDE>::value ? 2 : 0) | (exa::pde_has_admissible<exa::UserPDE>::value ? 4 : 0);
+}
 static exa::FvCellData make_cd(double* out, const double* centre, double t, double h, const exa::FvGridArgs* grid) {
     exa::FvCellData cd{out, centre, t, h, nullptr, {1, 1, 1}, nullptr, 0};
     if (grid) { cd.out = grid->out; cd.bstate = grid->bstate; cd.lam = grid->lam; cd.grid_on = 1; for (int a = 0; a < 3; a++) cd.g[a] = grid->g[a]; }

@@ -12,6 +12,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include "exa_launch.hpp"
+#include "exa_lim_detect.hpp"
 #include "exa_pde.hpp"
 
 namespace exa {
@@ -449,8 +450,6 @@ static bool lim_launch_all(K kern, long n, hipStream_t s, Args... args) {
     return true;
 }
 
-#define EXA_LIM_CASES(X) X(2) X(3) X(4) X(5) X(6) X(7) X(8)
-
 // EXA_LIM_PER_VARIABLE=1 in the environment routes five-variable systems through the per-variable kernels too (the path every
 // other variable count takes): lets one process compare the two (tests/test_limiter.py).  Read at every call: it is a test switch.
 static bool lim_per_variable() {
@@ -558,208 +557,21 @@ int limiter_reconstruct(int dim, int N, int Ns, int nv, const double* patch, con
 }
 
 // ------------------------------------------------------------------------------------------------------------------
-// A-posteriori (MOOD) detection: two HBM-bound passes over u[cell][node][var], a cell's contiguous block per workgroup
-// (N^dim > 64 nodes) or per wave (four cells per workgroup).
-//   limiter_snapshot_kernel   u^n -> u_old (skipped if null) and bounds[cell][4] = min rho, max rho, min E, max E
-//   limiter_detect_kernel     candidate -> mask byte: not finite / rho <= floor / p <= floor at a node, or the nodal range of
-//                             rho or E leaves [lo - delta, hi + delta] of the bounds of the cell and its face neighbours
-// Euler layout: rho first, energy last, min(3, nv - 2) momenta behind rho, gamma = 1.4.  Minima travel negated so that one
-// max-reduction serves every value; min / max are exact, so the result does not depend on the reduction order.
+// A-posteriori (MOOD) detection: the kernels live in exa_lim_detect.hpp, parameterised by a criterion type.  Here: the built-in
+// criterion -- Euler layout with a run-time variable count (five variables: compile-time), bounds[cell][4] = min rho, max rho, min E, max E.
+// Generated term sets that carry their own criterion instantiate the same kernels in their side library (lim_user.hip).
 // ------------------------------------------------------------------------------------------------------------------
-struct LimFaceKinds { int k[6]; };          // include/exahype_hip.h EXA_LIM_FACE_*
-
-template <int DIM, int N> struct LimScan {
-    static constexpr int NN = DIM == 3 ? N * N * N : N * N;
-    static constexpr int TPC = NN <= 64 ? 64 : 256;                // threads per cell
-    static constexpr int CPB = 256 / TPC;                          // cells per workgroup
-};
-
-__device__ inline double lim_max(double a, double b) { return a > b ? a : b; }
-
-// max over the TPC threads of a cell; every thread of the cell gets the result.  red: [4 waves][K]
-template <int K, int TPC>
-__device__ inline void lim_reduce_max(double (&m)[K], double* red) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1)
-#pragma unroll
-        for (int k = 0; k < K; k++) m[k] = lim_max(m[k], __shfl_xor(m[k], off, 64));
-    if constexpr (TPC == 256) {
-        const int wave = threadIdx.x >> 6;
-        if ((threadIdx.x & 63) == 0)
-#pragma unroll
-            for (int k = 0; k < K; k++) red[wave * K + k] = m[k];
-        __syncthreads();
-#pragma unroll
-        for (int w = 0; w < 4; w++)
-#pragma unroll
-            for (int k = 0; k < K; k++) m[k] = lim_max(m[k], red[w * K + k]);
-    }
-}
-
-template <int DIM, int N, int NV>
-__global__ void __launch_bounds__(256)
-limiter_snapshot_kernel(int nv_rt, long ncells, const double* __restrict__ u, double* __restrict__ u_old, double* __restrict__ bounds) {
-    using LS = LimScan<DIM, N>;
-    constexpr int TPC = LS::TPC;
-    __shared__ double red[4 * 4];
-    const int nv = NV ? NV : nv_rt;
-    const int len = LS::NN * nv;
-    const int t = threadIdx.x % TPC;
-    const long cell = (long)blockIdx.x * LS::CPB + threadIdx.x / TPC;
-    const bool live = cell < ncells;
-    const double ninf = -__builtin_huge_val();
-    double m[4] = {ninf, ninf, ninf, ninf};                        // -min rho, max rho, -min E, max E
-    if (live) {
-        const double* src = u + cell * len;
-        double* dst = u_old ? u_old + cell * len : nullptr;
-#pragma unroll 4
-        for (int i = t; i < len; i += TPC) {
-            const double x = src[i];
-            if (dst) dst[i] = x;
-            const int v = i % nv;
-            if (v == 0) { m[0] = lim_max(m[0], -x); m[1] = lim_max(m[1], x); }
-            if (v == nv - 1) { m[2] = lim_max(m[2], -x); m[3] = lim_max(m[3], x); }
-        }
-    }
-    lim_reduce_max<4, TPC>(m, red);
-    if (live && t == 0) {
-        double* b = bounds + cell * 4;
-        b[0] = -m[0]; b[1] = m[1]; b[2] = -m[2]; b[3] = m[3];
-    }
-}
-
-template <int DIM, int N, int NV>
-__global__ void __launch_bounds__(256)
-limiter_detect_kernel(int nv_rt, long nc0, long nc1, long nc2, const double* __restrict__ u, const double* __restrict__ bounds,
-                      LimGhosts gb, LimFaceKinds fk, double d0, double eps, double floor, unsigned char* __restrict__ mask) {
-    using LS = LimScan<DIM, N>;
-    constexpr int TPC = LS::TPC, NN = LS::NN;
-    extern __shared__ __attribute__((aligned(16))) double lim_sm[];            // [cells per workgroup][NN][nv]
-    __shared__ double red[4 * 5];
-    const int nv = NV ? NV : nv_rt;
-    const int len = NN * nv;
-    const int t = threadIdx.x % TPC;
-    const long nc[3] = {nc0, nc1, DIM == 3 ? nc2 : 1};
-    const long ncells = nc[0] * nc[1] * nc[2];
-    const long cell = (long)blockIdx.x * LS::CPB + threadIdx.x / TPC;
-    const bool live = cell < ncells;
-    double* q = lim_sm + (size_t)(threadIdx.x / TPC) * len;
-    const double ninf = -__builtin_huge_val();
-    double m[5] = {ninf, ninf, ninf, ninf, 0.0};                   // -min rho, max rho, -min E, max E, troubled
-    if (live) {
-        const double* src = u + cell * len;
-#pragma unroll 4
-        for (int i = t; i < len; i += TPC) {
-            const double x = src[i];
-            q[i] = x;
-            if (!(__builtin_fabs(x) <= 1.7976931348623157e308)) m[4] = 1.0;      // NaN, +-inf
-            const int v = i % nv;
-            if (v == 0) { m[0] = lim_max(m[0], -x); m[1] = lim_max(m[1], x); }
-            if (v == nv - 1) { m[2] = lim_max(m[2], -x); m[3] = lim_max(m[3], x); }
-        }
-    }
-    __syncthreads();
-    if (live) {
-        const int nm = nv - 2 < 3 ? nv - 2 : 3;
-        for (int n = t; n < NN; n += TPC) {
-            const double* s = q + n * nv;
-            const double rho = s[0];
-            double ke = 0.0;
-            for (int a = 0; a < nm; a++) ke += s[1 + a] * s[1 + a];
-            const double p = 0.4 * (s[nv - 1] - 0.5 * ke / rho);
-            if (!(rho > floor) || !(p > floor)) m[4] = 1.0;        // (written so that NaN counts as troubled)
-        }
-    }
-    lim_reduce_max<5, TPC>(m, red);
-    if (live && t == 0) {
-        long cc[3];
-        { long b = cell; cc[2] = b % nc[2]; b /= nc[2]; cc[1] = b % nc[1]; cc[0] = b / nc[1]; }
-        const double* own = bounds + cell * 4;
-        double lo[2] = {own[0], own[2]}, hi[2] = {own[1], own[3]};
-        for (int a = 0; a < DIM; a++)
-            for (int side = 0; side < 2; side++) {
-                const double* b;
-                const int kind = fk.k[a * 2 + side];
-                if (kind != 0 && cc[a] == (side ? nc[a] - 1 : 0)) {
-                    if (kind != 1) continue;                       // a face with a boundary condition: no neighbour
-                    long tc = 0;
-                    for (int c = 0; c < DIM; c++)
-                        if (c != a) tc = tc * nc[c] + cc[c];
-                    b = gb.layer[a * 2 + side] + tc * 4;           // the neighbour block's bounds arrived by exchange
-                } else {
-                    long nb[3] = {cc[0], cc[1], cc[2]};
-                    nb[a] = (nb[a] + (side ? 1 : nc[a] - 1)) % nc[a];
-                    b = bounds + ((nb[0] * nc[1] + nb[1]) * nc[2] + nb[2]) * 4;
-                }
-                for (int k = 0; k < 2; k++) {
-                    lo[k] = b[2 * k] < lo[k] ? b[2 * k] : lo[k];
-                    hi[k] = b[2 * k + 1] > hi[k] ? b[2 * k + 1] : hi[k];
-                }
-            }
-        bool bad = m[4] != 0.0;
-        for (int k = 0; k < 2; k++) {
-            const double delta = lim_max(d0, eps * (hi[k] - lo[k]));
-            const double cmin = -m[2 * k], cmax = m[2 * k + 1];
-            if (!(cmax <= hi[k] + delta) || !(cmin >= lo[k] - delta)) bad = true;
-        }
-        mask[cell] = bad ? 1 : 0;
-    }
-}
-
 int limiter_snapshot(int dim, int N, int nv, long ncells, const double* u, double* u_old, double* bounds, hipStream_t s) {
-    if (ncells <= 0) return 0;
-    switch (N) {
-#define X(NN_)                                                                                                                         \
-    case NN_: {                                                                                                                        \
-        const unsigned g2 = (unsigned)((ncells + LimScan<2, NN_>::CPB - 1) / LimScan<2, NN_>::CPB);                                    \
-        const unsigned g3 = (unsigned)((ncells + LimScan<3, NN_>::CPB - 1) / LimScan<3, NN_>::CPB);                                    \
-        if (dim == 2 && nv == 5) hipLaunchKernelGGL((limiter_snapshot_kernel<2, NN_, 5>), dim3(g2), dim3(256), 0, s, nv, ncells, u, u_old, bounds);  \
-        else if (dim == 2) hipLaunchKernelGGL((limiter_snapshot_kernel<2, NN_, 0>), dim3(g2), dim3(256), 0, s, nv, ncells, u, u_old, bounds);        \
-        else if (nv == 5) hipLaunchKernelGGL((limiter_snapshot_kernel<3, NN_, 5>), dim3(g3), dim3(256), 0, s, nv, ncells, u, u_old, bounds);         \
-        else hipLaunchKernelGGL((limiter_snapshot_kernel<3, NN_, 0>), dim3(g3), dim3(256), 0, s, nv, ncells, u, u_old, bounds);                      \
-        break;                                                                                                                         \
-    }
-        EXA_LIM_CASES(X)
-#undef X
-    default: set_error("limiter: N = %d is not built", N); return -1;
-    }
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) { set_error("limiter_snapshot launch: %s", hipGetErrorString(e)); return -2; }
-    return 0;
+    return nv == 5 ? lim_snapshot_launch<LimEulerCrit<5>>(dim, N, nv, ncells, u, u_old, bounds, s)
+                   : lim_snapshot_launch<LimEulerCrit<0>>(dim, N, nv, ncells, u, u_old, bounds, s);
 }
 
 int limiter_detect(int dim, int N, int nv, const long* nc, const double* u, const double* bounds, const LimGhosts* ghosts, const int* kinds,
                    double d0, double eps, double floor, unsigned char* mask, hipStream_t s) {
-    const long nc2 = dim == 3 ? nc[2] : 1;
-    const long ncells = nc[0] * nc[1] * nc2;
-    if (ncells <= 0) return 0;
-    LimGhosts gb{};
-    if (ghosts) gb = *ghosts;
-    LimFaceKinds fk{};
-    for (int f = 0; f < 2 * dim; f++) fk.k[f] = kinds ? kinds[f] : 0;
-    long nn = 1;
-    for (int a = 0; a < dim; a++) nn *= N;
-    const size_t bytes = sizeof(double) * (size_t)nn * nv * (nn <= 64 ? 4 : 1);
-    if (bytes > 64 * 1024) { set_error("limiter_detect: a cell of %ld nodes x %d variables does not fit the kernel's LDS buffer", nn, nv); return -1; }
-    switch (N) {
-#define X(NN_)                                                                                                                         \
-    case NN_: {                                                                                                                        \
-        const unsigned g2 = (unsigned)((ncells + LimScan<2, NN_>::CPB - 1) / LimScan<2, NN_>::CPB);                                    \
-        const unsigned g3 = (unsigned)((ncells + LimScan<3, NN_>::CPB - 1) / LimScan<3, NN_>::CPB);                                    \
-        if (dim == 2 && nv == 5) hipLaunchKernelGGL((limiter_detect_kernel<2, NN_, 5>), dim3(g2), dim3(256), bytes, s, nv, nc[0], nc[1], nc2, u, bounds, gb, fk, d0, eps, floor, mask); \
-        else if (dim == 2) hipLaunchKernelGGL((limiter_detect_kernel<2, NN_, 0>), dim3(g2), dim3(256), bytes, s, nv, nc[0], nc[1], nc2, u, bounds, gb, fk, d0, eps, floor, mask);       \
-        else if (nv == 5) hipLaunchKernelGGL((limiter_detect_kernel<3, NN_, 5>), dim3(g3), dim3(256), bytes, s, nv, nc[0], nc[1], nc2, u, bounds, gb, fk, d0, eps, floor, mask);        \
-        else hipLaunchKernelGGL((limiter_detect_kernel<3, NN_, 0>), dim3(g3), dim3(256), bytes, s, nv, nc[0], nc[1], nc2, u, bounds, gb, fk, d0, eps, floor, mask);                     \
-        break;                                                                                                                         \
-    }
-        EXA_LIM_CASES(X)
-#undef X
-    default: set_error("limiter: N = %d is not built", N); return -1;
-    }
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) { set_error("limiter_detect launch: %s", hipGetErrorString(e)); return -2; }
-    return 0;
+    return nv == 5 ? lim_detect_launch<LimEulerCrit<5>>(dim, N, nv, nc, u, bounds, ghosts, kinds, d0, eps, floor, mask, s)
+                   : lim_detect_launch<LimEulerCrit<0>>(dim, N, nv, nc, u, bounds, ghosts, kinds, d0, eps, floor, mask, s);
 }
+
 
 // ------------------------------------------------------------------------------------------------------------------
 // Conservative DG / FV interface.  A troubled cell T takes the FV patch update, its untroubled face neighbour D keeps

@@ -117,7 +117,7 @@ def _arity(fn):
 
 
 class SympyPDE:
-    def __init__(self, n_vars, flux, max_eigenvalue, max_dim=3, name="user", source=None, ncp=None, max_aux=None):
+    def __init__(self, n_vars, flux, max_eigenvalue, max_dim=3, name="user", source=None, ncp=None, max_aux=None, admissible=None, dmp=None):
         """flux(q, d) -> n_vars expressions, max_eigenvalue(q, d) -> one, in the state symbols q; d = 0-based normal.
         source(q) -> n_vars expressions (optional): the algebraic source S(q) of q_t + div F(q) = S(q) -- the hook the
         reference's harness declares beside flux and maxEigenvalue (`Unit test/correctness_test.cpp:16-23`).  It enters the
@@ -134,7 +134,15 @@ class SympyPDE:
         source(q, x, t), x = (x0, x1, x2) -- generate a term set with HAS_XT; the FV patch kernels hand it the volume centres
         (`exa_fv_time_step_device_oop`: cell centres and t; the in-place call: patches centred at the origin, t = 0), ADER-DG the node
         coordinates and level times (`exa_dg_plan_set_origin_time`).  Term sets with HAS_XT or an ncp run ADER-DG through a plain,
-        untuned stage-A kernel (2-D N <= 8, 3-D N <= 6); the tuned kernels serve the others."""
+        untuned stage-A kernel (2-D N <= 8, 3-D N <= 6); the tuned kernels serve the others.
+
+        admissible(q) -> 1..4 expressions g_k in the state symbols, dmp=(i, j, ...) -> 0..4 distinct variable indices (both optional): what the
+        a-posteriori subcell limiter (SubcellLimiter.step_a_posteriori / run) checks for this system.  A node is admissible iff every
+        g_k(q) > floor (IEEE arithmetic; a NaN is not admissible), and the relaxed discrete maximum principle watches the variables `dmp`
+        (() = positivity and finiteness only).  `dmp` alone is allowed (no expression, K_ADM = 0); `admissible` alone watches nothing.  With
+        either, the generated struct carries HAS_ADMISSIBLE and the side library its own instantiation of the detection kernels
+        (csrc/lim_user.hip); without both, the detector assumes the Euler layout (density first, energy last) and the generated source is
+        what it was."""
         if not 1 <= n_vars <= 8:
             raise ValueError("n_vars must be 1..8")
         self.n_vars, self.max_dim, self.name = n_vars, max_dim, name
@@ -172,6 +180,22 @@ class SympyPDE:
         xt = set(self.x) | {self.t}
         every = [e for f in self.flux_exprs for e in f] + self.eig_exprs + (self.source_exprs or []) + [e for f in (self.ncp_exprs or []) for e in f]
         self.uses_xt = any(e.free_symbols & xt for e in every)
+        self.adm_exprs = self.dmp_vars = None
+        if admissible is not None or dmp is not None:
+            self.adm_exprs = [sympy.sympify(e) for e in admissible(self.q)] if admissible is not None else []
+            if admissible is not None and not 1 <= len(self.adm_exprs) <= 4:
+                raise ValueError("admissible(q) must return 1 to 4 expressions, got %d" % len(self.adm_exprs))
+            if any(e.free_symbols & xt for e in self.adm_exprs):
+                raise ValueError("admissible(q): the expressions must depend on the state alone, not on x / t")
+            if any(e.free_symbols - set(self.q) for e in self.adm_exprs):
+                raise ValueError("admissible(q): unknown symbols %s" % sorted(str(x) for e in self.adm_exprs for x in e.free_symbols - set(self.q)))
+            self.dmp_vars = [int(i) for i in (dmp if dmp is not None else ())]
+            if len(self.dmp_vars) > 4:
+                raise ValueError("dmp: at most 4 variables, got %d" % len(self.dmp_vars))
+            if any(not 0 <= i < n_vars for i in self.dmp_vars):
+                raise ValueError("dmp: variable indices must be in 0..%d, got %s" % (n_vars - 1, self.dmp_vars))
+            if len(set(self.dmp_vars)) != len(self.dmp_vars):
+                raise ValueError("dmp: duplicate variable indices %s" % self.dmp_vars)
         self._lib = None
         self._id = None
 
@@ -406,6 +430,7 @@ class SympyPDE:
                 src_member += ("%s    __device__ static inline void %s {\n        switch (d) {\n%s\n"
                                "        default:\n            for (int v = 0; v < NV; v++) out[v] = 0.0;\n        }\n    }\n"
                                % ("" if fast else "    static constexpr bool HAS_NCP = true;\n", sig, "\n".join(cases)))
+        src_member += self._admissible_member()
         if self.uses_xt:
             fast_cases = ["        case %d: {\n%s\n        } break;" % (d, self._block(self.flux_exprs[d], ["F[%d]" % v for v in range(n)], "            ", fast=True))
                           for d in range(self.max_dim)]
@@ -414,6 +439,22 @@ class SympyPDE:
                            "        default:\n            for (int v = 0; v < NV; v++) F[v] = 0.0;\n        }\n    }\n" % "\n".join(fast_cases))
             return self._source_xt(flux_cases, eig_cases, src_member)
         return self._source_tuned(flux_cases, eig_cases, src_member)
+
+    def _admissible_member(self):
+        """HAS_ADMISSIBLE, K_ADM, K_DMP, DMP_VAR / dmp_var and admissible(q, g) -- IEEE division: the mask must not depend on an 11-ulp reciprocal"""
+        if self.adm_exprs is None:
+            return ""
+        ka, kd = len(self.adm_exprs), len(self.dmp_vars)
+        pick = "".join("k == %d ? %d : " % (k, v) for k, v in enumerate(self.dmp_vars)) + "0"
+        body = self._block(self.adm_exprs, ["g[%d]" % k for k in range(ka)], "        ") if ka else ""
+        return ("    // what the a-posteriori subcell limiter checks (exa_lim_detect.hpp): admissible iff every g[k] > floor; the discrete maximum principle watches DMP_VAR\n"
+                "    static constexpr bool HAS_ADMISSIBLE = true;\n"
+                "    static constexpr int K_ADM = %d;\n"
+                "    static constexpr int K_DMP = %d;\n"
+                "    static constexpr int DMP_VAR[%d] = {%s};\n"
+                "    __host__ __device__ static constexpr int dmp_var(int k) { return %s; }\n"
+                "    __device__ static inline void admissible(const double* q, double* g) {\n%s\n    }\n"
+                % (ka, kd, max(kd, 1), ", ".join(str(v) for v in self.dmp_vars) or "0", pick, body))
 
     def _tuned_flux_members(self):
         """aux / aux_fast bodies, flux<D> / flux_scaled<D> branches and the Dir member for a flux that depends on the state alone"""
@@ -589,6 +630,9 @@ struct UserPDE {
         for f in ("dg_inst.hip", "fv_rusanov.hip", "exa_dg_kernels.hpp", "exa_dg_stream.hpp", "exa_dg_reg.hpp", "exa_dg_fused.hpp",
                   "exa_dg_common.hpp", "exa_launch.hpp", "exa_pde.hpp", "exa_dg_plain.hpp", "exa_dg_m8.hpp", "exa_dg_boundary.hpp"):
             h.update(open(os.path.join(CSRC, f), "rb").read())
+        if self.adm_exprs is not None:                                 # (the detector unit is built for such term sets only)
+            for f in ("lim_user.hip", "exa_lim_detect.hpp"):
+                h.update(open(os.path.join(CSRC, f), "rb").read())
         h.update(open(os.path.join(os.path.dirname(os.path.abspath(__file__)), "build.py"), "rb").read())      # (compiler flags)
         h.update(repr(self.dg_flags).encode())
         h.update(os.environ.get("EXA_EXTRA_FLAGS", "").encode())       # (development builds with extra -D macros: a library of their own)
@@ -620,6 +664,8 @@ struct UserPDE {
                  ("dg_inst.hip", "dg2b.o", ["-DEXA_DIM=2", "-DEXA_UNIT_B"])]
         if self.max_dim >= 3:
             units += [("dg_inst.hip", "dg3.o", ["-DEXA_DIM=3", "-DEXA_UNIT_A"] + sched), ("dg_inst.hip", "dg3b.o", ["-DEXA_DIM=3", "-DEXA_UNIT_B"])]
+        if self.adm_exprs is not None:                                 # the term set's own a-posteriori detector (exa_user_lim_snapshot / _detect)
+            units.append(("lim_user.hip", "lim.o", []))
         procs = [(o, subprocess.Popen(common + extra + ["-c", os.path.join(CSRC, src), "-o", os.path.join(d, o)],
                                       stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, env=_build.compiler_env())) for src, o, extra in units]
         for o, p in procs:
@@ -636,4 +682,32 @@ struct UserPDE {
         if self._id is None:
             from . import _lib
             self._id = _lib.register_pde(self.build())
+            if self.adm_exprs is not None:
+                REGISTERED[self._id] = self
         return self._id
+
+    def admissible_values(self, q):
+        """The admissibility expressions g_k evaluated on q = [q_0, ..] (numpy arrays or torch tensors of one shape, anything with
+        arithmetic operators): a list of K_ADM arrays.  Rational powers only (what operators give): SubcellLimiter.run(track=True)'s statistics
+        and the tests' restatement use it, the kernels never."""
+        def ev(e):
+            if e.is_Symbol:
+                return q[self.q.index(e)]
+            if e.is_Number:
+                return float(e)
+            if e.is_Add or e.is_Mul:
+                out = ev(e.args[0])
+                for a in e.args[1:]:
+                    out = out + ev(a) if e.is_Add else out * ev(a)
+                return out
+            if e.is_Pow and e.exp.is_Rational:
+                return ev(e.base) ** (int(e.exp) if e.exp.is_Integer else float(e.exp))
+            raise ValueError("admissible_values: %s is not built from +, *, / and rational powers" % e)
+        out = []
+        for e in self.adm_exprs or []:
+            v = ev(e)
+            out.append(v if hasattr(v, "shape") else q[0] * 0 + v)
+        return out
+
+
+REGISTERED = {}     # pde id -> SympyPDE with its own admissibility criterion, registered in this process (SubcellLimiter.run(track=True))

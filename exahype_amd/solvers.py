@@ -981,6 +981,12 @@ AderDgSolver.run = _dg_run
 # ----------------------------------------------------------------------------------------------
 # FV subcell limiter (BASELINE configs[4])
 # ----------------------------------------------------------------------------------------------
+def _admissible_of(pde):
+    """The SympyPDE registered under this pde id in this process, if it carries its own admissibility criterion (else None)"""
+    from . import pde_codegen
+    return pde_codegen.REGISTERED.get(int(pde))
+
+
 class SubcellLimiter:
     """Limited ADER-DG step: untroubled cells take the DG step, troubled cells the FV Rusanov patch update
     (patch_size 2p+1, halo 1 -- the reference's kernel shape) of their projected data.  step(dt, mask) takes the troubled
@@ -1304,7 +1310,8 @@ class SubcellLimiter:
     # -- a-posteriori (MOOD) limiting --------------------------------------------------------------
     def _mood_setup(self):
         """Buffers of the a-posteriori step, allocated once: u_old (a second copy of u: DOUBLES the memory of the degrees of freedom),
-        bounds[cell][4], the mask bytes, and on a sharded grid the exchange of the boundary layers' bounds."""
+        bounds[cell][exa_lim_bounds_count] (4: min / max of density and energy; a term set with its own criterion: 2 per watched variable, none
+        with dmp=()), the mask bytes, and on a sharded grid the exchange of the boundary layers' bounds."""
         torch = _torch()
         s = self.s
         if s._one_kernel or s._fused:
@@ -1319,27 +1326,29 @@ class SubcellLimiter:
             raise MemoryError("SubcellLimiter: the a-posteriori step keeps u^n beside the candidate: %.1f GB more, %.1f GB of device memory "
                               "are free" % (need / 1e9, free / 1e9))
         ncell = int(np.prod(s.nc))
-        self._bounds = torch.zeros((ncell, 4), dtype=torch.float64, device=s.dev)
+        self._nb = int(s.lib.exa_lim_bounds_count(s._plan))
+        self._bounds = torch.zeros((ncell, self._nb), dtype=torch.float64, device=s.dev)
         self._mask = torch.zeros(tuple(s.nc), dtype=torch.bool, device=s.dev)
         self.hx_bounds = None
-        if s.halo is not None:
-            self.hx_bounds = HaloExchange(s.part, s.nc, 4, s.dev, stage_through_host=s.halo.stage)
+        if s.halo is not None and self._nb > 0:                # (nothing watched: nothing to exchange)
+            self.hx_bounds = HaloExchange(s.part, s.nc, self._nb, s.dev, stage_through_host=s.halo.stage)
         self._face_kind = self._face_kinds()
         self._u_old = torch.empty_like(s._u)
 
     def _snapshot(self, u, u_old):
         """bounds of u (and its copy into u_old, unless None); on a sharded grid the neighbours' boundary-layer bounds are exchanged."""
         s = self.s
+        nb = self._nb
         check(s.lib.exa_lim_snapshot(s._plan, C.c_void_p(u.data_ptr()), C.c_void_p(u_old.data_ptr()) if u_old is not None else None,
-                                     C.c_void_p(self._bounds.data_ptr()), _stream_ptr()))
+                                     C.c_void_p(self._bounds.data_ptr()) if nb else None, _stream_ptr()))
         hx = self.hx_bounds
         if hx is not None:
             nc3 = s.nc + [1] * (3 - s.dim)
-            b = self._bounds.reshape(nc3 + [4])
+            b = self._bounds.reshape(nc3 + [nb])
             for d in range(s.dim):
                 if s.part.partitioned(d):
-                    hx.send[d * 2 + 0].copy_(b.select(d, 0).reshape(-1, 4))
-                    hx.send[d * 2 + 1].copy_(b.select(d, nc3[d] - 1).reshape(-1, 4))
+                    hx.send[d * 2 + 0].copy_(b.select(d, 0).reshape(-1, nb))
+                    hx.send[d * 2 + 1].copy_(b.select(d, nc3[d] - 1).reshape(-1, nb))
             hx.start()
             hx.finish()
 
@@ -1347,7 +1356,7 @@ class SubcellLimiter:
         """mask (bool [nc..], device) of the candidate u against the bounds of the last _snapshot"""
         s = self.s
         ghosts = self.hx_bounds.ghost_ptrs() if self.hx_bounds is not None else None
-        check(s.lib.exa_lim_detect(s._plan, C.c_void_p(u.data_ptr()), C.c_void_p(self._bounds.data_ptr()), ghosts, self._face_kind,
+        check(s.lib.exa_lim_detect(s._plan, C.c_void_p(u.data_ptr()), C.c_void_p(self._bounds.data_ptr()) if self._nb else None, ghosts, self._face_kind,
                                    float(d0), float(eps), float(floor), C.c_void_p(self._mask.data_ptr()), _stream_ptr()))
         return self._mask
 
@@ -1428,7 +1437,9 @@ class SubcellLimiter:
 
         monitor(limiter, step, count): called after every step (count: 0-dim device tensor).
         track=True: self.stats = {"min_rho", "min_p", "max_troubled", "finite"} as 0-dim device tensors, running over every step's
-        result (torch passes over u: for tests and examples; reading them is the only synchronisation).
+        result (torch passes over u: for tests and examples; reading them is the only synchronisation).  For a term set with its own
+        criterion (SympyPDE(admissible=..., dmp=...), registered through its register()) "min_rho" / "min_p" give way to "min_admissible":
+        a device tensor [K_ADM] of the running minima of its expressions g_k, evaluated by tensor ops.
         conservative, rounds: see step_a_posteriori (lambda_max is scanned after the last round).  With track=True, stats then also holds
         "unresolved": the number of cells one more detection after the last round would still mark, summed over the steps (one extra
         detection pass per step)."""
@@ -1438,11 +1449,19 @@ class SubcellLimiter:
         if conservative:
             self._conservative_setup("run")
         steps = 0
+        own = bool(s.lib.exa_pde_flags(int(s.pde)) & 4)          # include/exahype_hip.h EXA_PDE_FLAG_ADMISSIBLE
         if track:
-            self.stats = {"min_rho": torch.full((), float("inf"), dtype=torch.float64, device=s.dev),
-                          "min_p": torch.full((), float("inf"), dtype=torch.float64, device=s.dev),
-                          "max_troubled": torch.zeros((), dtype=torch.int64, device=s.dev),
+            self.stats = {"max_troubled": torch.zeros((), dtype=torch.int64, device=s.dev),
                           "finite": torch.ones((), dtype=torch.bool, device=s.dev)}
+            if own:
+                adm = _admissible_of(int(s.pde))
+                if adm is None:
+                    raise ValueError("SubcellLimiter.run(track=True): term set %d carries its own admissibility criterion but was not registered through "
+                                     "SympyPDE.register() in this process, so its expressions are not known here" % int(s.pde))
+                self.stats["min_admissible"] = torch.full((len(adm.adm_exprs),), float("inf"), dtype=torch.float64, device=s.dev)
+            else:
+                self.stats["min_rho"] = torch.full((), float("inf"), dtype=torch.float64, device=s.dev)
+                self.stats["min_p"] = torch.full((), float("inf"), dtype=torch.float64, device=s.dev)
             if conservative:
                 self.stats["unresolved"] = torch.zeros((), dtype=torch.int64, device=s.dev)
         while s.time < t_end * (1 - 1e-14) and steps < max_steps:
@@ -1459,10 +1478,15 @@ class SubcellLimiter:
                 st = self.stats
                 if conservative:
                     st["unresolved"] = st["unresolved"] + (self._detect(u, d0, eps, floor) & ~self._mask_cum).sum()
-                rho = u[..., 0]
-                ke = sum(u[..., 1 + a] ** 2 for a in range(min(3, s.nv - 2)))
-                st["min_rho"] = torch.minimum(st["min_rho"], rho.min())
-                st["min_p"] = torch.minimum(st["min_p"], (0.4 * (u[..., s.nv - 1] - 0.5 * ke / rho)).min())
+                if own:
+                    if len(adm.adm_exprs):
+                        g = adm.admissible_values([u[..., v] for v in range(s.nv)])
+                        st["min_admissible"] = torch.minimum(st["min_admissible"], torch.stack([x.min() for x in g]))
+                else:
+                    rho = u[..., 0]
+                    ke = sum(u[..., 1 + a] ** 2 for a in range(min(3, s.nv - 2)))
+                    st["min_rho"] = torch.minimum(st["min_rho"], rho.min())
+                    st["min_p"] = torch.minimum(st["min_p"], (0.4 * (u[..., s.nv - 1] - 0.5 * ke / rho)).min())
                 st["max_troubled"] = torch.maximum(st["max_troubled"], count)
                 st["finite"] = st["finite"] & torch.isfinite(u).all()
             if monitor is not None:

@@ -72,9 +72,11 @@ int exa_register_pde(const char* library_path, int* pde_id);
 /* What a registered term set carries (0 for the built-in ones): EXA_PDE_FLAG_XT -- its terms depend on position / time (they see the
  * coordinates the kernels hand them; exa_pde_eval_device and exa_dg_max_eigenvalue, which have none, evaluate them at x = 0, t = 0:
  * use exa_pde_eval_device_at for the CFL scan of such a term set, as exahype_amd/solvers.py does);
- * EXA_PDE_FLAG_NCP -- it carries a non-conservative product. */
+ * EXA_PDE_FLAG_NCP -- it carries a non-conservative product;
+ * EXA_PDE_FLAG_ADMISSIBLE -- it says itself what the a-posteriori limiter's detector checks (exa_lim_snapshot / exa_lim_detect below). */
 #define EXA_PDE_FLAG_XT 1
 #define EXA_PDE_FLAG_NCP 2
+#define EXA_PDE_FLAG_ADMISSIBLE 4
 int exa_pde_flags(int pde);
 
 /* ---- point-wise PDE terms (Functions.h:2-3) ---------------------------------- */
@@ -286,7 +288,17 @@ int exa_dg_project_patches_ghost(exa_dg_plan* plan, const double* u_dev, const l
  * EXA_LIM_FACE_PERIODIC the periodic wrap inside the block; EXA_LIM_FACE_GHOST the neighbour block, whose boundary layer's bounds
  * are in ghost_bounds_dev[d*2+side][transverse cell][4] (transverse cells lexicographic over the other axes, the last fastest);
  * EXA_LIM_FACE_NONE a domain face with a boundary condition: no neighbour, the cell's own bounds.  ghost_bounds_dev may be NULL
- * if no face is EXA_LIM_FACE_GHOST.  min / max are exact: the mask does not depend on the order of the reductions. */
+ * if no face is EXA_LIM_FACE_GHOST.  min / max are exact: the mask does not depend on the order of the reductions.
+ * A registered term set with EXA_PDE_FLAG_ADMISSIBLE (pde_codegen.SympyPDE(admissible=..., dmp=...)) replaces the Euler layout by its own
+ * criterion; both entries then dispatch to kernels in its side library, same signatures:
+ *   (a) a value at a node is not finite, or !(g_k(q) > floor) for one of its K_ADM (0..4) admissibility expressions g_k (IEEE arithmetic);
+ *   (b) the relaxed discrete maximum principle as above on each of its K_DMP (0..4) watched variables v_0, v_1, ... in the order given:
+ *       bounds_dev[cell][2 K_DMP] = min v_0, max v_0, min v_1, ..., and ghost_bounds_dev[d*2+side][transverse cell][2 K_DMP].
+ * With K_DMP = 0 nothing is watched: no bounds are written or read (bounds_dev and the ghost bounds may be NULL), (a) alone decides.
+ * Such a term set may have one variable; without the flag exa_lim_detect refuses n_vars < 2 (it needs a density and an energy).
+ * exa_lim_bounds_count: doubles per cell of bounds_dev (and per transverse cell of the ghost bounds): 4 without the flag, 2 K_DMP with
+ * it, 0 for a NULL plan. */
+long exa_lim_bounds_count(const exa_dg_plan* plan);
 #define EXA_LIM_FACE_PERIODIC 0
 #define EXA_LIM_FACE_GHOST 1
 #define EXA_LIM_FACE_NONE 2
