@@ -6,47 +6,7 @@ import numpy as np
 import pytest
 import sympy
 
-G = 9.81
-
-
-def swe():
-    from exahype_amd.pde_codegen import SympyPDE
-
-    def flux(q, d):
-        h, hu, hv = q
-        un = (hu, hv)[d] / h if d < 2 else 0
-        p = sympy.Rational(1, 2) * G * h * h
-        f = [h * un, hu * un, hv * un]
-        if d < 2:
-            f[1 + d] = f[1 + d] + p
-        return f
-
-    def eig(q, d):
-        h, hu, hv = q
-        un = (hu, hv)[d] / h if d < 2 else 0
-        return sympy.Abs(un) + sympy.sqrt(G * h)
-    return SympyPDE(3, flux, eig, max_dim=2, name="shallow_water")
-
-
-def euler_sympy():
-    from exahype_amd.pde_codegen import SympyPDE
-
-    def prim(q):
-        irho = 1 / q[0]
-        p = sympy.Float(0.4) * (q[4] - sympy.Rational(1, 2) * irho * (q[1] ** 2 + q[2] ** 2 + q[3] ** 2))
-        return irho, p
-
-    def flux(q, d):
-        irho, p = prim(q)
-        c = irho * q[d + 1]
-        f = [c * q[0], c * q[1], c * q[2], c * q[3], c * q[4] + c * p]
-        f[d + 1] = f[d + 1] + p
-        return f
-
-    def eig(q, d):
-        irho, p = prim(q)
-        return sympy.Abs(q[d + 1] * irho) + sympy.sqrt(sympy.Float(1.4) * p * irho)
-    return SympyPDE(5, flux, eig, max_dim=3, name="euler_from_sympy")
+from tests.user_term_sets import G, euler_gravity, euler_sympy, swe, two_layer_like   # noqa: F401  (shared with tests/fv_user_cases.py)
 
 
 def reaction_advection(k=3.0, max_dim=3):
@@ -381,17 +341,6 @@ def test_source_term_fv_rusanov_vs_numpy():
 
 
 
-def euler_gravity(g=(0.3, -0.5, 0.8)):
-    """Compressible Euler with a constant body force: a NONLINEAR five-variable system with a source, S = (0, rho g, m . g)."""
-    from exahype_amd.pde_codegen import SympyPDE
-    base = euler_sympy()
-    q = base.q
-    return SympyPDE(5, flux=lambda qq, d: [e.subs(dict(zip(q, qq))) for e in base.flux_exprs[d]],
-                    max_eigenvalue=lambda qq, d: base.eig_exprs[d].subs(dict(zip(q, qq))),
-                    source=lambda qq: [0, qq[0] * g[0], qq[0] * g[1], qq[0] * g[2], qq[1] * g[0] + qq[2] * g[1] + qq[3] * g[2]],
-                    max_dim=3, name="euler_gravity")
-
-
 @pytest.mark.gpu
 @pytest.mark.parametrize("N,nc", [(6, (2, 2, 1)), (8, (1, 1, 2)), (4, (2, 1, 2))])
 def test_nonlinear_five_variable_source_aderdg_vs_numpy_oracle(N, nc):
@@ -658,15 +607,6 @@ def test_cell_data_flavour_through_the_printer():
 
 
 # ---- non-conservative product ------------------------------------------------------------------------------------------------------------
-def two_layer_like(max_dim=2):
-    """A system with a flux AND a non-conservative product (the shape of two-layer shallow water: the coupling of the layers is B(q) grad q):
-    q0_t + div(a q0) + k q1 grad q0 = 0,  q1_t + div(b q1) + k q0 grad q1 = 0."""
-    from exahype_amd.pde_codegen import SympyPDE
-    a, b, k = (1.0, 0.5, -0.25), (0.75, -0.5, 0.5), 0.3
-    return SympyPDE(2, flux=lambda q, d: [a[d] * q[0], b[d] * q[1]], max_eigenvalue=lambda q, d: sympy.Float(1.5),
-                    ncp=lambda q, dq, d: [k * q[1] * dq[0], k * q[0] * dq[1]], max_dim=max_dim, name="two_layer_like")
-
-
 def test_ncp_reaches_the_generated_device_code():
     src = two_layer_like().source()
     assert "HAS_NCP = true" in src and "ncp(const double* q, const double* dq, int d, double* out)" in src and "*dq[0]*q[1];" in src
