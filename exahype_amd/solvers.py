@@ -251,6 +251,16 @@ class HaloExchange:
             self.send[d * 2 + 0].copy_(lo.reshape(-1, self.ts))
             self.send[d * 2 + 1].copy_(hi.reshape(-1, self.ts))
 
+    def exchange_layers(self, block):
+        """block [nc0, nc1, nc2, ts]: its first and last layer along every partitioned axis go to the neighbours (the whole exchange:
+        filled, started and finished); they arrive in `ghost`."""
+        for d in range(self.part.dim):
+            if self.part.partitioned(d):
+                self.send[d * 2 + 0].copy_(block.select(d, 0).reshape(-1, self.ts))
+                self.send[d * 2 + 1].copy_(block.select(d, self.nc[d] - 1).reshape(-1, self.ts))
+        self.start()
+        self.finish()
+
     def start(self):
         import torch.distributed as dist
         ops, self._staged = [], []
@@ -718,6 +728,37 @@ class AderDgSolver:
         if timed:
             self.exchange_events.append((ready, c0, c1, i0, i1, p1))
 
+    def _cfl_dt(self, lam, cfl, t_end, who):
+        """dt = cfl * min(dx) / ((2p+1) * d * lambda_max), at most the time left to t_end, from the scanned lam (1-element device tensor): the
+        Dirichlet states are taken in and, with a partition, the maximum is reduced over the ranks (the only true collective of the scheme).
+        Raises on a non-finite eigenvalue (_cfl_step)."""
+        if self.boundary:
+            lam = self.boundary_eigenvalue(lam)
+        if self.part is not None and self.part.world > 1:
+            import torch.distributed as dist
+            dist.all_reduce(lam, op=dist.ReduceOp.MAX)
+        return _cfl_step(float(lam[0]), cfl * min(self.dx) / ((2 * self.N - 1) * self.dim), t_end - self.time, who)
+
+    def run(self, t_end, cfl=0.4, max_steps=1000000):
+        """Advance until `self.time` reaches t_end (as FVPatchGrid.run; r4 integrated a DURATION from a local t = 0 here) with the CFL step of
+        _cfl_dt.  Returns the number of steps; raises on a non-finite eigenvalue."""
+        torch = _torch()
+        steps, lam = 0, None
+        fuse = self.can_fuse_cfl_scan()        # r5: the scan of step n + 1 rides in stage B of step n (one pass over u per step less); the first step scans
+        try:
+            if fuse:
+                self._cfl_out = torch.zeros(1, dtype=torch.float64, device=self.dev)
+            while self.time < t_end * (1 - 1e-14) and steps < max_steps:
+                if lam is None:
+                    lam = self.max_eigenvalue()
+                dt = self._cfl_dt(lam, cfl, t_end, "AderDgSolver.run")
+                self.step(dt)
+                lam = self._cfl_out if fuse else None
+                steps += 1
+        finally:
+            self._cfl_out = None
+        return steps
+
     def __del__(self):
         try:
             self.lib.exa_dg_plan_destroy(self._plan)
@@ -948,36 +989,6 @@ def _cfl_step(lam, scale, left, who):
     return min(scale / lam, left) if lam > 0.0 else left
 
 
-def _dg_run(self, t_end, cfl=0.4, max_steps=1000000):
-    """Advance until `self.time` reaches t_end (as FVPatchGrid.run; r4 integrated a DURATION from a local t = 0 here) with the CFL step
-    dt = cfl * min(dx) / ((2p+1) * d * lambda_max); with a partition the maximum eigenvalue is reduced over the ranks (the only true collective
-    of the scheme).  Returns the number of steps; raises on a non-finite eigenvalue."""
-    torch = _torch()
-    steps, lam = 0, None
-    fuse = self.can_fuse_cfl_scan()        # r5: the scan of step n + 1 rides in stage B of step n (one pass over u per step less); the first step scans
-    try:
-        if fuse:
-            self._cfl_out = torch.zeros(1, dtype=torch.float64, device=self.dev)
-        while self.time < t_end * (1 - 1e-14) and steps < max_steps:
-            if lam is None:
-                lam = self.max_eigenvalue()
-            if self.boundary:
-                lam = self.boundary_eigenvalue(lam)
-            if self.part is not None and self.part.world > 1:
-                import torch.distributed as dist
-                dist.all_reduce(lam, op=dist.ReduceOp.MAX)
-            dt = _cfl_step(float(lam[0]), cfl * min(self.dx) / ((2 * self.N - 1) * self.dim), t_end - self.time, "AderDgSolver.run")
-            self.step(dt)
-            lam = self._cfl_out if fuse else None
-            steps += 1
-    finally:
-        self._cfl_out = None
-    return steps
-
-
-AderDgSolver.run = _dg_run
-
-
 # ----------------------------------------------------------------------------------------------
 # FV subcell limiter (BASELINE configs[4]; SURVEY.md A.6)
 # ----------------------------------------------------------------------------------------------
@@ -985,6 +996,13 @@ def _admissible_of(pde):
     """The SympyPDE registered under this pde id in this process, if it carries its own admissibility criterion (else None)"""
     from . import pde_codegen
     return pde_codegen.REGISTERED.get(int(pde))
+
+
+def _euler_pressure(u):
+    """p = 0.4 (E - |m|^2 / (2 rho)) of u[..., nv] in the Euler layout: density first, energy last, min(3, nv - 2) momenta behind the density"""
+    nv = u.shape[-1]
+    ke = sum(u[..., 1 + a] ** 2 for a in range(min(3, nv - 2)))
+    return 0.4 * (u[..., nv - 1] - 0.5 * ke / u[..., 0])
 
 
 class SubcellLimiter:
@@ -1038,7 +1056,9 @@ class SubcellLimiter:
         self._ovf_host = torch.zeros(1, dtype=torch.uint8).pin_memory()
         self._ovf_event = torch.cuda.Event()
         self._ovf_event.record(torch.cuda.current_stream(solver.dev))
-        self.hx_mask = self.hx_layer = None
+        self.hx_mask = self.hx_layer = self.hx_bounds = None
+        self._fvflux = self._mask_cum = None                   # the conservative interface's buffers (_conservative_setup)
+        self._u_old = self._bounds = self._mask = None         # the a-posteriori step's (_mood_setup)
         self._bc_layers = {}              # (d, side) -> ghost subcell layer [transverse cells][Ns^(dim-1)][n_vars] of a domain face
         for d, side, _, _, _ in solver._bc:
             nt = ncell // solver.nc[d]
@@ -1048,6 +1068,7 @@ class SubcellLimiter:
             self.hx_mask = HaloExchange(solver.part, solver.nc, 1, solver.dev, stage_through_host=stage)
             self.hx_layer = HaloExchange(solver.part, solver.nc, self.Ns ** (solver.dim - 1) * solver.nv, solver.dev,
                                          stage_through_host=stage)
+        self._face_kind = self._face_kinds()
 
     def operators(self):
         N, Ns = self.s.N, self.Ns
@@ -1067,8 +1088,7 @@ class SubcellLimiter:
         u = s.u
         nodes = tuple(range(dim, 2 * dim))
         rho = u[..., 0]
-        ke = sum(u[..., 1 + a] ** 2 for a in range(min(3, s.nv - 2)))
-        p = 0.4 * (u[..., s.nv - 1] - 0.5 * ke / rho)
+        p = _euler_pressure(u)
         bad = (rho.amin(nodes) <= floor) | (p.amin(nodes) <= floor) | ~torch.isfinite(u).all(-1).flatten(dim).all(-1)
         w = torch.as_tensor(s.operators()["w"], device=u.device)
         mean = rho
@@ -1077,16 +1097,8 @@ class SubcellLimiter:
         lo, hi = mean.clone(), mean.clone()
         ghost = None
         if s.halo is not None:                                   # neighbour means across block faces
-            hx = self.hx_mask
-            nc3 = s.nc + [1] * (3 - dim)
-            m3 = mean.reshape(nc3)
-            for d in range(dim):
-                if s.part.partitioned(d):
-                    hx.send[d * 2 + 0].copy_(m3.select(d, 0).reshape(-1, 1))
-                    hx.send[d * 2 + 1].copy_(m3.select(d, nc3[d] - 1).reshape(-1, 1))
-            hx.start()
-            hx.finish()
-            ghost = hx.ghost
+            self.hx_mask.exchange_layers(mean.reshape(self.hx_mask.nc + [1]))
+            ghost = self.hx_mask.ghost
         for d in range(dim):
             up, dn = mean.roll(-1, d), mean.roll(1, d)
             if ghost is not None and s.part.partitioned(d):
@@ -1149,13 +1161,7 @@ class SubcellLimiter:
         the solver's).  Returns the ghost-layer pointer array."""
         s, hm, hl = self.s, self.hx_mask, self.hx_layer
         u = s.u if u is None else u
-        nc3 = s.nc + [1] * (3 - s.dim)
-        for d in range(s.dim):
-            if s.part.partitioned(d):
-                hm.send[d * 2 + 0].copy_(m.select(d, 0).reshape(-1, 1))
-                hm.send[d * 2 + 1].copy_(m.select(d, nc3[d] - 1).reshape(-1, 1))
-        hm.start()
-        hm.finish()
+        hm.exchange_layers(m.unsqueeze(-1))
         for d in range(s.dim):
             if not s.part.partitioned(d):
                 continue
@@ -1189,16 +1195,27 @@ class SubcellLimiter:
         else:
             m = torch.as_tensor(np.ascontiguousarray(mask), dtype=torch.bool).to(s.dev, non_blocking=True)
         m = m.reshape(-1)
-        count = self._compact(m)
-        self._project(m, s.u, s.time)
-        if conservative:
-            self._face_flux()
         t0 = s.time
+        count = self._patches_of(m, s.u, t0, conservative)
         s.step(dt)                                             # candidate DG solution everywhere
-        self._update_and_reconstruct(dt, t0)
-        if conservative:
-            self._interface_correct(m.contiguous(), dt)
+        self._replace(dt, t0, m if conservative else None)
         return count
+
+    def _patches_of(self, m, u, t, face_flux):
+        """First half of every limited step: the cells of m (bool [n_cells], device) compacted, their FV patches projected from the state u at
+        time t, and -- for the conservative interface -- the patches' FV face fluxes.  Returns the troubled count (0-dim)."""
+        count = self._compact(m)
+        self._project(m, u, t)
+        if face_flux:
+            self._face_flux()
+        return count
+
+    def _replace(self, dt, t0, correct_outside=None):
+        """Second half: the compacted cells of the solver's u take the FV update of their patches over [t0, t0 + dt]; correct_outside (bool
+        mask over the cells, device): the conservative interface -- their face neighbours outside that mask are corrected."""
+        self._update_and_reconstruct(dt, t0)
+        if correct_outside is not None:
+            self._interface_correct(correct_outside.contiguous(), dt)
 
     def _one_volume_size(self, who):
         # the FV patch update takes ONE volume size h (the reference's generated `time_step` has no cell size at all: SURVEY.md Appendix B): a grid with
@@ -1277,7 +1294,7 @@ class SubcellLimiter:
         [capacity][2 dim][n_vars][N^(dim-1)] and the cumulative mask of a step."""
         torch = _torch()
         s = self.s
-        if getattr(self, "_fvflux", None) is not None:
+        if self._fvflux is not None:
             return
         if s.halo is not None:
             raise ValueError("SubcellLimiter.%s(conservative=True): the grid is partitioned; the exchange of the FV face fluxes between the "
@@ -1290,7 +1307,6 @@ class SubcellLimiter:
             raise ValueError("SubcellLimiter.%s(conservative=True): built for the built-in Euler (5 variables) and advection (1 variable) term sets; "
                              "term set %d with %d variables%s is not served" % (who, int(s.pde), s.nv, " (position / time dependent terms or a "
                                                                                 "non-conservative product)" if flags & 3 else ""))
-        self._cons_kind = self._face_kinds()
         self._mask_cum = torch.zeros(tuple(s.nc), dtype=torch.bool, device=s.dev)
         self._fvflux = torch.zeros((self.capacity, s.lib.exa_lim_face_flux_count(s._plan)), dtype=torch.float64, device=s.dev)
 
@@ -1304,7 +1320,7 @@ class SubcellLimiter:
         """The untroubled (mask == 0; bool tensor over the cells, device) face neighbours of the compacted cells trade F* for the FV face flux"""
         s = self.s
         check(s.lib.exa_lim_interface_correct(s._plan, C.c_void_p(s.u.data_ptr()), C.c_void_p(s.trace.data_ptr()), C.c_void_p(self._cells.data_ptr()),
-                                              self.capacity, C.c_void_p(mask.data_ptr()), self._cons_kind, C.c_void_p(self._fvflux.data_ptr()),
+                                              self.capacity, C.c_void_p(mask.data_ptr()), self._face_kind, C.c_void_p(self._fvflux.data_ptr()),
                                               dt, darr(s.dx), _stream_ptr()))
 
     # -- a-posteriori (MOOD) limiting --------------------------------------------------------------
@@ -1318,7 +1334,7 @@ class SubcellLimiter:
             raise ValueError("SubcellLimiter: the a-posteriori step needs the two-kernel solver step (u^n and the candidate in separate arrays, "
                              "no pending corrector); construct the solver with one_kernel_step=False%s"
                              % (", fused_single_stage=False" if s._fused else ""))
-        if getattr(self, "_u_old", None) is not None:
+        if self._u_old is not None:
             return
         need = s._u.numel() * 8
         free = torch.cuda.mem_get_info(s.dev)[0]
@@ -1329,10 +1345,8 @@ class SubcellLimiter:
         self._nb = int(s.lib.exa_lim_bounds_count(s._plan))
         self._bounds = torch.zeros((ncell, self._nb), dtype=torch.float64, device=s.dev)
         self._mask = torch.zeros(tuple(s.nc), dtype=torch.bool, device=s.dev)
-        self.hx_bounds = None
         if s.halo is not None and self._nb > 0:                # (nothing watched: nothing to exchange)
             self.hx_bounds = HaloExchange(s.part, s.nc, self._nb, s.dev, stage_through_host=s.halo.stage)
-        self._face_kind = self._face_kinds()
         self._u_old = torch.empty_like(s._u)
 
     def _snapshot(self, u, u_old):
@@ -1341,16 +1355,8 @@ class SubcellLimiter:
         nb = self._nb
         check(s.lib.exa_lim_snapshot(s._plan, C.c_void_p(u.data_ptr()), C.c_void_p(u_old.data_ptr()) if u_old is not None else None,
                                      C.c_void_p(self._bounds.data_ptr()) if nb else None, _stream_ptr()))
-        hx = self.hx_bounds
-        if hx is not None:
-            nc3 = s.nc + [1] * (3 - s.dim)
-            b = self._bounds.reshape(nc3 + [nb])
-            for d in range(s.dim):
-                if s.part.partitioned(d):
-                    hx.send[d * 2 + 0].copy_(b.select(d, 0).reshape(-1, nb))
-                    hx.send[d * 2 + 1].copy_(b.select(d, nc3[d] - 1).reshape(-1, nb))
-            hx.start()
-            hx.finish()
+        if self.hx_bounds is not None:
+            self.hx_bounds.exchange_layers(self._bounds.reshape(self.hx_bounds.nc + [nb]))
 
     def _detect(self, u, d0, eps, floor):
         """mask (bool [nc..], device) of the candidate u against the bounds of the last _snapshot"""
@@ -1394,38 +1400,25 @@ class SubcellLimiter:
         self._one_volume_size("step_a_posteriori")
         self._mood_setup()
         if conservative:
-            return self._step_conservative(dt, d0, eps, floor, int(rounds))
-        self.check()
-        t0 = s.time
-        self._snapshot(s.u, self._u_old)
-        s.step(dt)                                             # candidate DG solution everywhere
-        m = self._detect(s.u, d0, eps, floor).reshape(-1)
-        count = self._compact(m)
-        self._project(m, self._u_old, t0)
-        self._update_and_reconstruct(dt, t0)
-        return count
-
-    def _step_conservative(self, dt, d0, eps, floor, rounds):
-        s = self.s
-        if rounds < 1:
-            raise ValueError("SubcellLimiter.step_a_posteriori: rounds must be >= 1")
-        self._conservative_setup("step_a_posteriori")
+            rounds = int(rounds)
+            if rounds < 1:
+                raise ValueError("SubcellLimiter.step_a_posteriori: rounds must be >= 1")
+            self._conservative_setup("step_a_posteriori")
         self.check()
         t0 = s.time
         self._snapshot(s.u, self._u_old)
         s.step(dt)                                             # candidate DG solution everywhere; its traces stay intact for the rounds
-        cum = self._mask_cum
-        cum.zero_()
+        cum = self._mask_cum if conservative else None
+        if conservative:
+            cum.zero_()
         total = None
-        for _ in range(rounds):                                # (a round without new cells launches over -1 slots)
-            new = self._detect(s.u, d0, eps, floor) & ~cum
-            cum |= new
-            m = new.reshape(-1)
-            count = self._compact(m)                           # the capacity holds per round: earlier rounds' patches are done with
-            self._project(m, self._u_old, t0)
-            self._face_flux()
-            self._update_and_reconstruct(dt, t0)
-            self._interface_correct(cum, dt)
+        for _ in range(rounds if conservative else 1):         # (a round without new cells launches over -1 slots)
+            new = self._detect(s.u, d0, eps, floor)
+            if conservative:                                   # only the NEWLY troubled cells; the plain step has one round and no cumulative mask
+                new = new & ~cum
+                cum |= new
+            count = self._patches_of(new.reshape(-1), self._u_old, t0, conservative)     # the capacity holds per round: earlier rounds' patches are done with
+            self._replace(dt, t0, cum)
             total = count if total is None else total + count
         return total
 
@@ -1465,14 +1458,8 @@ class SubcellLimiter:
             if conservative:
                 self.stats["unresolved"] = torch.zeros((), dtype=torch.int64, device=s.dev)
         while s.time < t_end * (1 - 1e-14) and steps < max_steps:
-            lam = s.max_eigenvalue()
-            if s.boundary:
-                lam = s.boundary_eigenvalue(lam)
-            if s.part is not None and s.part.world > 1:
-                import torch.distributed as dist
-                dist.all_reduce(lam, op=dist.ReduceOp.MAX)
-            dt = _cfl_step(float(lam[0]), cfl * min(s.dx) / ((2 * s.N - 1) * s.dim), t_end - s.time, "SubcellLimiter.run")
-            count = self.step_a_posteriori(dt, d0, eps, floor, conservative, rounds) if conservative else self.step_a_posteriori(dt, d0, eps, floor)
+            dt = s._cfl_dt(s.max_eigenvalue(), cfl, t_end, "SubcellLimiter.run")
+            count = self.step_a_posteriori(dt, d0, eps, floor, conservative, rounds)
             if track:
                 u = s.u
                 st = self.stats
@@ -1483,10 +1470,8 @@ class SubcellLimiter:
                         g = adm.admissible_values([u[..., v] for v in range(s.nv)])
                         st["min_admissible"] = torch.minimum(st["min_admissible"], torch.stack([x.min() for x in g]))
                 else:
-                    rho = u[..., 0]
-                    ke = sum(u[..., 1 + a] ** 2 for a in range(min(3, s.nv - 2)))
-                    st["min_rho"] = torch.minimum(st["min_rho"], rho.min())
-                    st["min_p"] = torch.minimum(st["min_p"], (0.4 * (u[..., s.nv - 1] - 0.5 * ke / rho)).min())
+                    st["min_rho"] = torch.minimum(st["min_rho"], u[..., 0].min())
+                    st["min_p"] = torch.minimum(st["min_p"], _euler_pressure(u).min())
                 st["max_troubled"] = torch.maximum(st["max_troubled"], count)
                 st["finite"] = st["finite"] & torch.isfinite(u).all()
             if monitor is not None:

@@ -1,16 +1,16 @@
 """numpy restatement of the a-posteriori (MOOD) subcell limiter for a term set that says itself what "admissible" means and which variables
 the relaxed discrete maximum principle watches (pde_codegen.SympyPDE(admissible=..., dmp=...); exa_lim_detect.hpp) -- for
-tests/test_limiter_admissible.py and scripts/make_limiter_admissible_golden.py.  Test infrastructure, built on tests/limiter_mood_ref.py
-(the Euler-layout restatement) and the oracle's ADER-DG step and projection / reconstruction operators; never imported by the product."""
+tests/test_limiter_admissible.py and scripts/make_limiter_admissible_golden.py: the general limiter of tests/limiter_ref.py (cell_bounds,
+neighbourhood, detect and its margin bookkeeping are that module's) with a criterion from SymPy expressions, a Rusanov update in numpy, and
+the shallow-water dam break.  Test infrastructure; never imported by the product."""
 import numpy as np
 import sympy
 
-from oracle import aderdg_numpy as A
-from oracle.dg_operators import operators
-from oracle.limiter_numpy import apply_all_axes, projection_matrix, reconstruction_matrix
 from tests import limiter_mood_ref as M
+from tests import limiter_ref as L
+from tests.limiter_ref import cell_bounds, detect, neighbourhood, reset_margin, smallest_margin  # noqa: F401  (the general limiter is this module's)
 
-D0, EPS, FLOOR = M.D0, M.EPS, M.FLOOR
+D0, EPS, FLOOR = L.D0, L.EPS, L.FLOOR
 G_SWE = 9.81
 
 
@@ -26,81 +26,6 @@ def criterion(spde):
         cols = [q[..., v] for v in range(q.shape[-1])]
         return [(np.broadcast_to(g(*cols), q.shape[:-1]), np.broadcast_to(sc(*cols), q.shape[:-1])) for g, sc in fs]
     return admissible
-
-
-def cell_bounds(u, dmp):
-    """bounds[grid.., 2 K] = min, max of every watched variable over the nodes of every cell (what exa_lim_snapshot writes)"""
-    dim = M._dim(u)
-    nodes = tuple(range(dim, 2 * dim))
-    cols = []
-    for v in dmp:
-        cols += [u[..., v].min(nodes), u[..., v].max(nodes)]
-    return np.stack(cols, axis=-1) if cols else np.zeros(u.shape[:dim] + (0,))
-
-
-def neighbourhood(bounds, no_neighbour=(), ghost=None):
-    """M.neighbourhood for bounds of any width 2 K: lo[grid.., K], hi[grid.., K]; ghost[(d, side)] = [transverse cells.., 2 K]"""
-    if ghost is None:
-        return M.neighbourhood(bounds, no_neighbour)
-    dim = bounds.ndim - 1
-    mins, maxs = bounds[..., 0::2], bounds[..., 1::2]
-    lo, hi = mins.copy(), maxs.copy()
-    for d in range(dim):
-        for side, shift in ((0, 1), (1, -1)):
-            nl, nh = np.roll(mins, shift, d), np.roll(maxs, shift, d)
-            edge = [slice(None)] * dim
-            edge[d] = 0 if side == 0 else -1
-            edge = tuple(edge)
-            if (d, side) in no_neighbour:
-                nl[edge], nh[edge] = mins[edge], maxs[edge]
-            elif (d, side) in ghost:
-                g = np.asarray(ghost[(d, side)]).reshape(mins[edge].shape[:-1] + (bounds.shape[-1],))
-                nl[edge], nh[edge] = g[..., 0::2], g[..., 1::2]
-            lo, hi = np.minimum(lo, nl), np.maximum(hi, nh)
-    return lo, hi
-
-
-_smallest = [np.inf]
-
-
-def reset_margin():
-    _smallest[0] = np.inf
-
-
-def smallest_margin():
-    """the smallest relative margin of every comparison detect() made since reset_margin()"""
-    return _smallest[0]
-
-
-def detect(cand, bounds, admissible, dmp, d0=D0, eps=EPS, floor=FLOOR, no_neighbour=(), ghost=None):
-    """(mask[grid..], margin[grid..]): troubled if (a) a value is not finite or not g_k > floor at a node for one of admissible(cand)'s
-    values, or (b) the nodal range of a watched variable leaves [lo - delta, hi + delta], delta = max(d0, eps (hi - lo)).  admissible:
-    q[..., nv] -> list of g_k or of (g_k, scale_k) (see criterion()), or None.  margin: the smallest relative distance of a decision
-    quantity of the cell from its threshold (g_k: relative to scale_k; inf for a cell with a non-finite value)."""
-    dim = M._dim(cand)
-    nodes = tuple(range(dim, 2 * dim))
-    grid = cand.shape[:dim]
-    with np.errstate(all="ignore"):
-        fin = np.isfinite(cand).all(-1).reshape(grid + (-1,)).all(-1)
-        bad = ~fin
-        margin = np.full(grid, np.inf)
-        for item in (admissible(cand) if admissible is not None else []):
-            g, scale = item if isinstance(item, tuple) else (item, None)
-            bad = bad | ~(g.min(nodes) > floor) | np.isnan(g).reshape(grid + (-1,)).any(-1)
-            rel = M._rel(g, floor) if scale is None else np.abs(g - floor) / np.maximum(scale, 1e-300)
-            margin = np.minimum(margin, rel.min(nodes))
-        if len(dmp):
-            lo, hi = neighbourhood(bounds, no_neighbour, ghost)
-            for k, v in enumerate(dmp):
-                q = cand[..., v]
-                l, h = lo[..., k], hi[..., k]
-                delta = np.maximum(d0, eps * (h - l))
-                qmax, qmin = q.max(nodes), q.min(nodes)
-                bad = bad | ~(qmax <= h + delta) | ~(qmin >= l - delta)
-                margin = np.minimum(margin, np.minimum(M._rel(qmax, h + delta), M._rel(qmin, l - delta)))
-        margin = np.where(fin, margin, np.inf)
-    _smallest[0] = min(_smallest[0], float(margin.min()))
-    return bad, margin
 
 
 # ---- the limited step for any term set with the interface of oracle/aderdg_numpy.py (flux, maxeig) ---------------------------------------
@@ -127,39 +52,9 @@ def fv_rusanov(pde, dim):
     return fv
 
 
-def replace_troubled(u, cand, mask, dt, dx, ops, fv):
-    """M.replace_troubled with the FV update given: cand with the troubled cells replaced by the FV patch update of the projected u"""
-    dim = M._dim(u)
-    N = ops["N"]
-    Ns = 2 * N - 1
-    P = projection_matrix(ops["xi"], Ns)
-    R = reconstruction_matrix(P, ops["w"])
-    out = cand.copy()
-    if not mask.any():
-        return out
-    proj = apply_all_axes(P, u, dim, dim)
-    S = Ns + 2
-    core = (slice(1, -1),) * dim
-    for idx in zip(*np.nonzero(mask)):
-        patch = np.pad(proj[idx], [(1, 1)] * dim + [(0, 0)], mode="edge")
-        for a in range(dim):
-            for side, off in ((0, -1), (1, +1)):
-                nb = list(idx)
-                nb[a] = (nb[a] + off) % u.shape[a]
-                sl = [slice(1, -1)] * dim
-                sl[a] = 0 if side == 0 else S - 1
-                patch[tuple(sl)] = np.take(proj[tuple(nb)], Ns - 1 if side == 0 else 0, axis=a)
-        patch = fv(patch, dt, dx[0] / Ns)
-        out[idx] = apply_all_axes(R, patch[core], dim, 0)
-    return out
-
-
 def step(u, dt, dx, ops, pde, admissible, dmp, d0=D0, eps=EPS, floor=FLOOR):
     """One a-posteriori limited step on a periodic grid: (u_new, mask)."""
-    with np.errstate(all="ignore"):
-        cand = A.step(u, dt, dx, ops, pde)
-        mask, _ = detect(cand, cell_bounds(u, dmp), admissible, dmp, d0, eps, floor)
-        return replace_troubled(u, cand, mask, dt, dx, ops, fv_rusanov(pde, M._dim(u))), mask
+    return L.step(u, dt, dx, ops, pde, admissible, dmp, fv_rusanov(pde, L._dim(u)), d0, eps, floor)
 
 
 # ---- shallow water (h, hu, hv), the periodic double dam break along x ------------------------------------------------------------------
@@ -196,7 +91,7 @@ def dam_initial(N, nx, dim=2):
 
 def depth_change(u, u0, w):
     """sum over the grid of the integral of |h - h0| in units of the cell volume"""
-    dim = M._dim(u)
+    dim = L._dim(u)
     v = np.abs(u[..., 0] - u0[..., 0])
     for _ in range(dim):
         v = np.tensordot(v, w, axes=([dim], [0]))
@@ -207,30 +102,14 @@ def run_dam_break(N, nx, dim=2, t_end=0.05, cfl=0.4, max_steps=100000):
     """The double dam break on nx x 1 cells with the CFL step of SubcellLimiter.run, criterion [h], dmp = (0,).  Returns steps, min_h (over
     every step's result), max_troubled (cells in one step), change = depth_change against the initial state, mass (relative defect of the
     total depth) -- or, if the run leaves the admissible states, what it had until then and "failed"."""
-    ops = operators(N)
-    w = ops["w"]
-    dx = [1.0 / nx] * dim
     u0 = dam_initial(N, nx, dim)
-    u = u0.copy()
     pde = ShallowWater()
-    t, steps, worst, min_h = 0.0, 0, 0, np.inf
-    out = dict(N=N, nx=nx, dim=dim, cfl=cfl, t_end=t_end)
-    while t < t_end * (1 - 1e-14) and steps < max_steps:
-        with np.errstate(all="ignore"):
-            lam = max(np.max(pde.maxeig(u, d)) for d in range(dim))
-        if not np.isfinite(lam):
-            out["failed"] = "lambda_max = %r at step %d" % (lam, steps)
-            break
-        dt = min(cfl * dx[0] / ((2 * N - 1) * dim * lam), t_end - t)
-        u, mask = step(u, dt, dx, ops, pde, swe_admissible, (0,))
-        t += dt
-        steps += 1
-        worst = max(worst, int(mask.sum()))
-        if not np.isfinite(u).all():
-            out["failed"] = "non-finite u after step %d" % steps
-            break
-        min_h = min(min_h, float(u[..., 0].min()))
-    out.update(steps=steps, min_h=min_h, max_troubled=worst)
+    out = dict(N=N, nx=nx, dim=dim, cfl=cfl, t_end=t_end, min_h=np.inf)
+
+    def track(u):
+        out["min_h"] = min(out["min_h"], float(u[..., 0].min()))
+    u, ops = L.run(u0.copy(), pde, N, nx, t_end, cfl, max_steps, lambda u, dt, dx, ops: step(u, dt, dx, ops, pde, swe_admissible, (0,)), track, out)
     if "failed" not in out:
+        w = ops["w"]
         out.update(change=depth_change(u, u0, w), mass=M.defects(M.totals(u0, w)[:1], M.totals(u, w)[:1])[0])
     return out

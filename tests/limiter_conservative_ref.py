@@ -19,10 +19,10 @@ bcs: {(axis, side): ("outflow",) | ("wall", sign[V])} as tests/dg_boundary_numpy
 import numpy as np
 
 from oracle import aderdg_numpy as A
-from oracle.dg_operators import operators
-from oracle.limiter_numpy import apply_all_axes, projection_matrix, reconstruction_matrix
+from oracle.limiter_numpy import apply_all_axes, build_patch, projection_matrix, reconstruction_matrix
 from tests import dg_boundary_numpy as B
 from tests import limiter_mood_ref as M
+from tests import limiter_ref as L
 
 U53 = 2.0 ** -53
 
@@ -48,34 +48,6 @@ def dg_step(u, dt, dx, ops, pde, bcs=None):
     st = A.step(u, dt, dx, ops, pde, stages=True)
     Ff = [np.concatenate([np.take(st["Fstar"][a], [u.shape[a] - 1], axis=a), st["Fstar"][a]], axis=a) for a in range(dim)]
     return st["unew"], Ff
-
-
-def build_patch(proj, idx, bcs=None):
-    """patch [(Ns + 2).., V] of cell idx from the projected state proj [grid.., Ns.., V]: interior, face halos = the adjacent subcell layer of the
-    face neighbours (periodic; at a domain face with a condition the cell's own adjacent layer, times the sign for a wall), edges / corners =
-    nearest interior value"""
-    dim = (proj.ndim - 1) // 2
-    Ns = proj.shape[dim]
-    S = Ns + 2
-    bcs = bcs or {}
-    patch = np.pad(proj[idx], [(1, 1)] * dim + [(0, 0)], mode="edge")
-    for a in range(dim):
-        for side, off in ((0, -1), (1, +1)):
-            sl = [slice(1, -1)] * dim
-            sl[a] = 0 if side == 0 else S - 1
-            bc = bcs.get((a, side))
-            if bc is not None and idx[a] == (0 if side == 0 else proj.shape[a] - 1):
-                layer = np.take(proj[idx], 0 if side == 0 else Ns - 1, axis=a)
-                if bc[0] == "wall":
-                    layer = layer * np.asarray(bc[1])
-                elif bc[0] != "outflow":
-                    raise ValueError(bc[0])
-            else:
-                nb = list(idx)
-                nb[a] = (nb[a] + off) % proj.shape[a]
-                layer = np.take(proj[tuple(nb)], Ns - 1 if side == 0 else 0, axis=a)
-            patch[tuple(sl)] = layer
-    return patch
 
 
 def face_fluxes(patch, pde):
@@ -182,31 +154,15 @@ def run_tube(N, nx, dim, rounds=3, t_end=0.1, cfl=0.4, max_steps=100000):
     """limiter_mood_ref.run_tube with the conservative step.  Returns steps, l1, min_rho, min_p (over every step's result), max_troubled
     (cells in one step's cumulative mask), unresolved (summed over the steps), cons (relative defect of every conserved total) -- or, if
     the run leaves the admissible states, what it had until then and "failed"."""
-    ops = operators(N)
-    w = ops["w"]
-    dx = [1.0 / nx] * dim
-    u = M.tube_initial(N, nx, dim)
+    u0 = M.tube_initial(N, nx, dim)
     pde = A.Euler()
-    m0 = M.totals(u, w)
-    t, steps, worst, unresolved, min_rho, min_p = 0.0, 0, 0, 0, np.inf, np.inf
-    out = dict(N=N, nx=nx, dim=dim, rounds=rounds)
-    while t < t_end * (1 - 1e-14) and steps < max_steps:
-        with np.errstate(all="ignore"):
-            lam = max(np.max(pde.maxeig(u, d)) for d in range(dim))
-        if not np.isfinite(lam):
-            out["failed"] = "lambda_max = %r at step %d" % (lam, steps)
-            break
-        dt = min(cfl * dx[0] / ((2 * N - 1) * dim * lam), t_end - t)
+    out = dict(N=N, nx=nx, dim=dim, rounds=rounds, unresolved=0)
+
+    def one(u, dt, dx, ops):
         u, mask, left = step(u, dt, dx, ops, rounds, pde=pde)
-        t += dt
-        steps += 1
-        worst = max(worst, int(mask.sum()))
-        unresolved += left
-        if not np.isfinite(u).all():
-            out["failed"] = "non-finite u after step %d" % steps
-            break
-        min_rho, min_p = min(min_rho, float(u[..., 0].min())), min(min_p, float(M.pressure(u).min()))
-    out.update(steps=steps, min_rho=min_rho, min_p=min_p, max_troubled=worst, unresolved=unresolved)
+        out["unresolved"] += left
+        return u, mask
+    u, ops = L.run(u0, pde, N, nx, t_end, cfl, max_steps, one, M.track_minima(out), out)
     if "failed" not in out:
-        out.update(l1=M.tube_l1(u, ops["xi"], w, t_end), cons=M.defects(m0, M.totals(u, w)))
+        out.update(l1=M.tube_l1(u, ops["xi"], ops["w"], t_end), cons=M.defects(M.totals(u0, ops["w"]), M.totals(u, ops["w"])))
     return out

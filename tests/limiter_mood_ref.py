@@ -1,22 +1,20 @@
 """numpy restatement of the a-posteriori (MOOD) subcell limiter -- SubcellLimiter.step_a_posteriori / run and the two kernels behind them
-(exa_lim_snapshot, exa_lim_detect) -- for tests/test_limiter_a_posteriori.py and scripts/make_limiter_mood_golden.py.  Test
-infrastructure: built on the oracle's ADER-DG step, projection / reconstruction operators and FV patch update, never imported by the
-product.
+(exa_lim_snapshot, exa_lim_detect) -- for tests/test_limiter_a_posteriori.py and scripts/make_limiter_mood_golden.py: the general limiter of
+tests/limiter_ref.py with the Euler criterion and the compiled oracle's FV patch update, and the double Sod tube.  Test infrastructure,
+never imported by the product.
 
 Euler layout: density first, energy last, min(3, nv - 2) momenta behind the density, gamma = 1.4."""
 import numpy as np
 
 import oracle
 from oracle import aderdg_numpy as A
-from oracle.dg_operators import operators
-from oracle.limiter_numpy import apply_all_axes, projection_matrix, reconstruction_matrix
+from oracle.dg_operators import operators  # noqa: F401  (the tests take it from here)
+from oracle.limiter_numpy import replace_troubled as _replace_troubled
+from tests import limiter_ref as L
+from tests.limiter_ref import _dim
 
 G = 1.4
-D0, EPS, FLOOR = 1e-4, 1e-3, 1e-12
-
-
-def _dim(u):
-    return (u.ndim - 1) // 2
+D0, EPS, FLOOR = L.D0, L.EPS, L.FLOOR
 
 
 def pressure(u):
@@ -26,64 +24,27 @@ def pressure(u):
         return 0.4 * (u[..., -1] - 0.5 * ke / u[..., 0])
 
 
+def admissible(u):
+    """the Euler criterion for limiter_ref.detect: [rho, (p, size of p's terms)].  The pressure's distance from the floor is taken relative to
+    0.4 (|E| + |m|^2 / (2 |rho|)): it is the one quantity whose rounding may differ between two evaluations."""
+    E, p = u[..., -1], pressure(u)
+    return [u[..., 0], (p, 0.4 * (np.abs(E) + np.abs(E - p / 0.4)))]
+
+
+def _dmp(u):
+    """the watched variables: density and energy"""
+    return (0, u.shape[-1] - 1)
+
+
 def cell_bounds(u):
     """bounds[grid.., 4] = min rho, max rho, min E, max E over the nodes of every cell (what exa_lim_snapshot writes)"""
-    dim = _dim(u)
-    nodes = tuple(range(dim, 2 * dim))
-    return np.stack([u[..., 0].min(nodes), u[..., 0].max(nodes), u[..., -1].min(nodes), u[..., -1].max(nodes)], axis=-1)
-
-
-def neighbourhood(bounds, no_neighbour=(), ghost=None):
-    """lo[grid.., 2], hi[grid.., 2] (rho, E): minimum / maximum of the bounds over the cell and its 2*dim face neighbours.  Periodic wrap;
-    (d, side) in no_neighbour: a domain face with a boundary condition, the cell's own bounds; ghost[(d, side)] = [transverse cells.., 4]:
-    the neighbour block's bounds across that block face."""
-    dim = bounds.ndim - 1
-    mins, maxs = bounds[..., 0::2], bounds[..., 1::2]
-    lo, hi = mins.copy(), maxs.copy()
-    for d in range(dim):
-        for side, shift in ((0, 1), (1, -1)):                 # side 0: the neighbour at c_d - 1
-            nl, nh = np.roll(mins, shift, d), np.roll(maxs, shift, d)
-            edge = [slice(None)] * dim
-            edge[d] = 0 if side == 0 else -1
-            edge = tuple(edge)
-            if (d, side) in no_neighbour:
-                nl[edge], nh[edge] = mins[edge], maxs[edge]
-            elif ghost is not None and (d, side) in ghost:
-                g = np.asarray(ghost[(d, side)]).reshape(mins[edge].shape[:-1] + (4,))
-                nl[edge], nh[edge] = g[..., 0::2], g[..., 1::2]
-            lo, hi = np.minimum(lo, nl), np.maximum(hi, nh)
-    return lo, hi
-
-
-def _rel(a, b):
-    """relative distance of a decision quantity from its threshold"""
-    return np.abs(a - b) / np.maximum(np.maximum(np.abs(a), np.abs(b)), 1e-300)
+    return L.cell_bounds(u, _dmp(u))
 
 
 def detect(cand, bounds, d0=D0, eps=EPS, floor=FLOOR, no_neighbour=(), ghost=None):
-    """(mask[grid..], margin[grid..]) of the candidate against the old state's bounds: troubled if (a) a value is not finite or rho <= floor or
-    p <= floor at a node, or (b) the nodal range of rho or E leaves [lo - delta, hi + delta], delta = max(d0, eps (hi - lo)).
-    margin: the smallest relative distance of a decision quantity of the cell from its threshold (inf for a cell with a non-finite value:
-    finiteness has no threshold).  The pressure's distance is taken relative to the size of its terms, 0.4 (|E| + |m|^2 / (2 |rho|)): it is
-    the one quantity whose rounding may differ between two evaluations."""
-    dim = _dim(cand)
-    nodes = tuple(range(dim, 2 * dim))
-    with np.errstate(all="ignore"):
-        rho, E, p = cand[..., 0], cand[..., -1], pressure(cand)
-        fin = np.isfinite(cand).all(-1).reshape(cand.shape[:dim] + (-1,)).all(-1)
-        bad = ~fin | ~(rho.min(nodes) > floor) | ~(p.min(nodes) > floor)
-        margin = _rel(rho, floor).min(nodes)
-        terms = 0.4 * (np.abs(E) + np.abs(E - p / 0.4))
-        margin = np.minimum(margin, (np.abs(p - floor) / np.maximum(terms, 1e-300)).min(nodes))
-        lo, hi = neighbourhood(bounds, no_neighbour, ghost)
-        for k, q in enumerate((rho, E)):
-            l, h = lo[..., k], hi[..., k]
-            delta = np.maximum(d0, eps * (h - l))
-            qmax, qmin = q.max(nodes), q.min(nodes)
-            bad |= ~(qmax <= h + delta) | ~(qmin >= l - delta)
-            margin = np.minimum(margin, np.minimum(_rel(qmax, h + delta), _rel(qmin, l - delta)))
-        margin = np.where(fin, margin, np.inf)
-    return bad, margin
+    """limiter_ref.detect with the Euler criterion: troubled if a value is not finite, rho <= floor or p <= floor at a node, or the nodal
+    range of rho or E leaves the relaxed range of the old state's bounds"""
+    return L.detect(cand, bounds, admissible, _dmp(cand), d0, eps, floor, no_neighbour, ghost)
 
 
 def detect_a_priori(u, w, dmp_tol=0.5, floor=1e-12):
@@ -110,41 +71,13 @@ def fv_update(dim, nv=5):
 
 
 def replace_troubled(u, cand, mask, dt, dx, ops):
-    """cand with the troubled cells replaced by the FV patch update of the projected u (oracle.limiter_numpy.limited_step with the
-    candidate given instead of computed; periodic grid)."""
-    dim = _dim(u)
-    N = ops["N"]
-    Ns = 2 * N - 1
-    P = projection_matrix(ops["xi"], Ns)
-    R = reconstruction_matrix(P, ops["w"])
-    fv = fv_update(dim, u.shape[-1])
-    out = cand.copy()
-    if not mask.any():
-        return out
-    proj = apply_all_axes(P, u, dim, dim)
-    S = Ns + 2
-    core = (slice(1, -1),) * dim
-    for idx in zip(*np.nonzero(mask)):
-        patch = np.pad(proj[idx], [(1, 1)] * dim + [(0, 0)], mode="edge")
-        for a in range(dim):
-            for side, off in ((0, -1), (1, +1)):
-                nb = list(idx)
-                nb[a] = (nb[a] + off) % u.shape[a]
-                sl = [slice(1, -1)] * dim
-                sl[a] = 0 if side == 0 else S - 1
-                patch[tuple(sl)] = np.take(proj[tuple(nb)], Ns - 1 if side == 0 else 0, axis=a)
-        patch = fv(patch, dt, dx[0] / Ns)
-        out[idx] = apply_all_axes(R, patch[core], dim, 0)
-    return out
+    """cand with the troubled cells replaced by the compiled oracle's FV patch update of the projected u (periodic grid)"""
+    return _replace_troubled(u, cand, mask, dt, dx, ops, fv_update(_dim(u), u.shape[-1]))
 
 
 def step(u, dt, dx, ops, pde=None, d0=D0, eps=EPS, floor=FLOOR):
     """One a-posteriori limited step on a periodic grid: (u_new, mask)."""
-    pde = pde or A.Euler()
-    with np.errstate(all="ignore"):
-        cand = A.step(u, dt, dx, ops, pde)
-        mask, _ = detect(cand, cell_bounds(u), d0, eps, floor)
-        return replace_troubled(u, cand, mask, dt, dx, ops), mask
+    return L.step(u, dt, dx, ops, pde or A.Euler(), admissible, _dmp(u), fv_update(_dim(u), u.shape[-1]), d0, eps, floor)
 
 
 # ---- the periodic double Sod tube along x ------------------------------------------------------------------------
@@ -214,39 +147,30 @@ def defects(m0, m1):
     return [float(abs(a - b) / max(abs(a), 1.0)) for a, b in zip(m0, m1)]
 
 
+def track_minima(out):
+    """the callback of limiter_ref.run that keeps min_rho, min_p over every step's result in out"""
+    out.update(min_rho=np.inf, min_p=np.inf)
+
+    def track(u):
+        out.update(min_rho=min(out["min_rho"], float(u[..., 0].min())), min_p=min(out["min_p"], float(pressure(u).min())))
+    return track
+
+
 def run_tube(N, nx, dim, t_end=0.1, cfl=0.4, a_priori=False, max_steps=100000):
     """The double tube on nx x 1 (x 1) cells with the CFL step of SubcellLimiter.run.  Returns steps, l1, min_rho, min_p (over every
     step's result), max_troubled (cells in one step), cons (relative defect of every conserved total) -- or, if the run leaves the
     admissible states, what it had until then and "failed"."""
-    ops = operators(N)
-    w = ops["w"]
-    dx = [1.0 / nx] * dim
-    u = tube_initial(N, nx, dim)
+    u0 = tube_initial(N, nx, dim)
     pde = A.Euler()
-    m0 = totals(u, w)
-    t, steps, worst, min_rho, min_p = 0.0, 0, 0, np.inf, np.inf
-    out = dict(N=N, nx=nx, dim=dim)
-    while t < t_end * (1 - 1e-14) and steps < max_steps:
+
+    def one(u, dt, dx, ops):
+        if not a_priori:
+            return step(u, dt, dx, ops, pde)
+        mask = detect_a_priori(u, ops["w"])
         with np.errstate(all="ignore"):
-            lam = max(np.max(pde.maxeig(u, d)) for d in range(dim))
-        if not np.isfinite(lam):
-            out["failed"] = "lambda_max = %r at step %d" % (lam, steps)
-            break
-        dt = min(cfl * dx[0] / ((2 * N - 1) * dim * lam), t_end - t)
-        if a_priori:
-            mask = detect_a_priori(u, w)
-            with np.errstate(all="ignore"):
-                u = replace_troubled(u, A.step(u, dt, dx, ops, pde), mask, dt, dx, ops)
-        else:
-            u, mask = step(u, dt, dx, ops, pde)
-        t += dt
-        steps += 1
-        worst = max(worst, int(mask.sum()))
-        if not np.isfinite(u).all():
-            out["failed"] = "non-finite u after step %d" % steps
-            break
-        min_rho, min_p = min(min_rho, float(u[..., 0].min())), min(min_p, float(pressure(u).min()))
-    out.update(steps=steps, min_rho=min_rho, min_p=min_p, max_troubled=worst)
+            return replace_troubled(u, A.step(u, dt, dx, ops, pde), mask, dt, dx, ops), mask
+    out = dict(N=N, nx=nx, dim=dim)
+    u, ops = L.run(u0, pde, N, nx, t_end, cfl, max_steps, one, track_minima(out), out)
     if "failed" not in out:
-        out.update(l1=tube_l1(u, ops["xi"], w, t_end), cons=defects(m0, totals(u, w)))
+        out.update(l1=tube_l1(u, ops["xi"], ops["w"], t_end), cons=defects(totals(u0, ops["w"]), totals(u, ops["w"])))
     return out

@@ -422,3 +422,34 @@ def test_default_mode_is_unchanged_bit_for_bit():
         out.append(lim.download())
         assert getattr(lim, "_fvflux", None) is None
     assert np.array_equal(out[0], out[1])
+
+
+@gpu
+@pytest.mark.parametrize("dim,N,nc", [(2, 4, (8, 2)), (3, 4, (8, 1, 2))])
+def test_a_posteriori_step_is_the_step_with_its_own_mask(dim, N, nc):
+    """One pipeline behind both entries: step_a_posteriori(dt) finds a mask m, and step(dt, m) from the same state gives the same bits; so
+    does one conservative round against step(dt, cumulative mask, conservative=True)."""
+    from exahype_amd import solvers as exa
+    from tests.test_limiter_a_posteriori import _oscillating_tube
+    u, _ = _oscillating_tube(dim, N, nc)
+    dx = [1.0 / nc[0]] * dim
+    dt = _dt(u, dx, dim, N)
+    ncells = int(np.prod(nc))
+    s = exa.AderDgSolver(dim, N, nc, dx=dx, one_kernel_step=False)
+    lim = exa.SubcellLimiter(s, capacity=ncells)
+
+    def fresh():
+        s.upload(u)
+        s.time = 0.0
+
+    for kw, found in (({}, "_mask"), ({"conservative": True, "rounds": 1}, "_mask_cum")):
+        fresh()
+        lim.step_a_posteriori(dt, **kw)
+        m = getattr(lim, found).clone()
+        u_found = lim.download()
+        fresh()
+        lim.step(dt, m, conservative=bool(kw))
+        u_given = lim.download()
+        print("dim %d N %d nc %s %s: %d of %d troubled" % (dim, N, nc, "conservative" if kw else "plain", int(m.sum()), ncells))
+        assert 0 < int(m.sum()) < ncells
+        assert np.array_equal(u_found, u_given)
