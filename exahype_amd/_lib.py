@@ -11,6 +11,7 @@ LIB_PATH = os.path.join(HERE, "lib", "libexahype_hip.so")
 
 PDE_EULER_REF2D, PDE_EULER, PDE_ADVECTION = 0, 1, 2
 FV_FAITHFUL, FV_RUSANOV = 0, 1
+FV_FACE_PERIODIC, FV_FACE_STATE, FV_FACE_MIRROR = 0, 1, 2      # include/exahype_hip.h EXA_FV_FACE_*
 
 # every symbol include/exahype_hip.h declares: (restype, argtypes)
 _vp, _dp, _lp = C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_long)
@@ -31,6 +32,7 @@ SIGNATURES = {
     "exa_fv_time_step_device_at": (C.c_int, [_vp, _vp, _vp, C.c_double, C.c_double, C.c_double, _vp]),
     "exa_fv_qout_count": (C.c_long, [_vp]),
     "exa_fv_grid_step_device": (C.c_int, [_vp, _vp, _vp, _lp, _vp, _vp, C.c_double, C.c_double, C.c_double, _vp, _vp]),
+    "exa_fv_grid_step_device_bc": (C.c_int, [_vp, _vp, _vp, _lp, C.POINTER(C.c_int), _vp, _vp, C.c_double, C.c_double, C.c_double, _vp, _vp]),
     "exa_fv_max_eigenvalue": (C.c_int, [_vp, _vp, C.c_int, _vp, C.c_double, C.c_double, _vp, _vp]),
     "exa_fv_time_step_device_masked": (C.c_int, [_vp, _vp, _vp, C.c_double, C.c_double, _vp]),
     "exa_fv_time_step_device_masked_at": (C.c_int, [_vp, _vp, _vp, _vp, C.c_double, C.c_double, C.c_double, _vp]),

@@ -1,8 +1,9 @@
-"""Boundary conditions of the ADER-DG solver at the faces of the domain (AderDgSolver(boundary=...)).
+"""Boundary conditions at the faces of the domain: AderDgSolver(boundary=...), the SubcellLimiter that follows it, and FVPatchGrid(boundary=...).
 
-A boundary is a dict {(axis, side): condition}, side 0 = low and 1 = high face; a face it does not name stays periodic.  Every condition
-prescribes the ghost trace stage B reads beyond the face, as the halo exchange does between blocks (include/exahype_hip.h
-exa_dg_boundary_ghost):
+A boundary is a dict {(axis, side): condition}, side 0 = low and 1 = high face; a face it does not name stays periodic.
+
+ADER-DG: every condition prescribes the ghost trace stage B reads beyond the face, as the halo exchange does between blocks
+(include/exahype_hip.h exa_dg_boundary_ghost):
 
   Outflow()          the cell's own outward trace: the Rusanov flux becomes F(q_in)
   Wall(sign=None)    state s * q_in and flux -s * F_in; a mirror image of the domain across the face for term sets with F_d(S q) = -S F_d(q),
@@ -10,11 +11,20 @@ exa_dg_boundary_ghost):
   Dirichlet(state)   a prescribed state: an array [n_vars] (constant), or a callable f(x, t) -> [n, n_vars] on device tensors, x: [n, 3]; the
                      ghost is then the time average over the step's Gauss time levels of f and of its normal flux
 
-This module needs neither torch nor a GPU: validate_boundary() is what the solver calls on its argument.
+FV patch grid: every condition prescribes the volumes of the halo layers beyond the face (include/exahype_hip.h exa_fv_grid_step_device_bc;
+fv_faces() below turns the dict into the kinds and the per-face data of that call):
+
+  Outflow()          the patch's own interior volume at the same distance inside the face (a mirror with every sign +1): the Rusanov flux at the
+                     face becomes F(q_in)
+  Wall(sign=None)    that mirror volume times s on the evolved variables, +1 on the auxiliary ones (sign=None as above)
+  Dirichlet(state)   a constant state [n_real + n_aux] in every volume beyond the face -- as a bare array means.  One state per face: a callable
+                     is refused (position- or time-dependent FV ghosts are not supported)
+
+This module needs neither torch nor a GPU: validate_boundary() / fv_faces() are what the solvers call on their argument.
 """
 import numpy as np
 
-from ._lib import PDE_EULER, PDE_EULER_REF2D
+from ._lib import FV_FACE_MIRROR, FV_FACE_PERIODIC, FV_FACE_STATE, PDE_EULER, PDE_EULER_REF2D
 
 BC_OUTFLOW, BC_WALL, BC_DIRICHLET = 1, 2, 3      # include/exahype_hip.h EXA_BC_*
 
@@ -111,3 +121,51 @@ def coefficients(bc, n_vars):
     if isinstance(bc, Wall):
         return np.concatenate([bc.sign, -bc.sign])
     return np.array(bc.state, dtype=np.float64) if bc.constant else None
+
+
+def fv_faces(boundary, dim, n_real, n_aux, pde):
+    """FVPatchGrid's boundary dict, resolved for exa_fv_grid_step_device_bc: (kinds [2 dim], data [2 dim][V], conditions), V = n_real + n_aux.
+    Face axis * 2 + side is FV_FACE_PERIODIC (not named), FV_FACE_STATE with its state as data (Dirichlet(constant) or a bare array,
+    broadcast to [V] as FVPatchGrid always did) or FV_FACE_MIRROR with its signs as data (Outflow: all +1; Wall: its sign on the n_real evolved
+    variables -- resolved by validate_boundary with n_real variables -- and +1 on the auxiliary ones).  conditions: {(axis, side): Outflow() |
+    Wall(sign [n_real]) | Dirichlet(state [V])}, what fill_halos_boundary takes.  Raises ValueError like validate_boundary, and on a callable
+    Dirichlet, a state that does not broadcast to [V] and a state that is not finite."""
+    V = n_real + n_aux
+    if not isinstance(boundary, dict):
+        raise ValueError("boundary: a dict {(axis, side): Outflow() | Wall(...) | Dirichlet(state) | state}, got %r" % type(boundary).__name__)
+    checked, states = {}, {}
+    for key, bc in boundary.items():
+        if isinstance(bc, (Outflow, Wall)):
+            checked[key] = bc
+            continue
+        if isinstance(bc, Dirichlet):
+            if not bc.constant:
+                raise ValueError("boundary: Dirichlet(function) at %r -- the FV grid takes one constant state per face" % (key,))
+            state = bc.state
+        else:
+            try:
+                state = np.asarray(bc, dtype=np.float64)
+            except (TypeError, ValueError):
+                raise ValueError("boundary: %r at %r is not Outflow(), Wall(...), Dirichlet(state) or a state" % (bc, key)) from None
+        try:
+            state = np.array(np.broadcast_to(state, (V,)))
+        except ValueError:
+            raise ValueError("boundary: the state at %r has shape %s, expected (%d,)" % (key, np.shape(state), V)) from None
+        if not np.all(np.isfinite(state)):
+            raise ValueError("boundary: the state at %r is not finite" % (key,))
+        checked[key] = Dirichlet(state[:n_real])
+        states[key] = state
+    resolved = validate_boundary(checked, dim, n_real, pde)          # (keys, wall signs)
+    states = {(int(k[0]), int(k[1])): v for k, v in states.items()}
+    kinds, data, conditions = [FV_FACE_PERIODIC] * (2 * dim), np.zeros((2 * dim, V)), {}
+    for (a, side), bc in resolved.items():
+        f = a * 2 + side
+        if isinstance(bc, Dirichlet):
+            kinds[f], data[f] = FV_FACE_STATE, states[(a, side)]
+            conditions[(a, side)] = Dirichlet(states[(a, side)])
+        else:
+            kinds[f], data[f] = FV_FACE_MIRROR, 1.0
+            if isinstance(bc, Wall):
+                data[f, :n_real] = bc.sign
+            conditions[(a, side)] = bc
+    return kinds, data, conditions

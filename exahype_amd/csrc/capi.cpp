@@ -257,26 +257,51 @@ int exa_fv_time_step_device_at(exa_fv_plan* p, double* Q_dev, const double* cent
                      centre_dev, t);
 }
 
-int exa_fv_grid_step_device(exa_fv_plan* p, const double* Q_dev, double* QNext_dev, const long* grid, const double* boundary_dev,
-                            const double* centre_dev, double t, double dt, double h, double* lambda_next_dev, void* stream) {
-    if (!p || !grid || ((!Q_dev || !QNext_dev) && p->count > 0)) { set_error("exa_fv_grid_step_device: NULL argument"); return EXA_ERR_INVALID; }
-    if (Q_dev == QNext_dev) { set_error("exa_fv_grid_step_device: the new states need an array of their own (the neighbours read the old ones)"); return EXA_ERR_INVALID; }
-    if (p->mode == EXA_FV_RUSANOV && !(h > 0.0)) { set_error("EXA_FV_RUSANOV needs the volume size h > 0"); return EXA_ERR_INVALID; }
-    FvGridArgs ga{QNext_dev, boundary_dev, {1, 1, 1}, lambda_next_dev};
+// the grid step behind both entries; who: the entry that was called (error messages)
+static int fv_grid_step(const char* who, exa_fv_plan* p, const double* Q_dev, double* QNext_dev, const long* grid, const int* face_kind, const double* face_data_dev,
+                        const double* centre_dev, double t, double dt, double h, double* lambda_next_dev, void* stream) {
+    if (!p || !grid || ((!Q_dev || !QNext_dev) && p->count > 0)) { set_error("%s: NULL argument", who); return EXA_ERR_INVALID; }
+    if (Q_dev == QNext_dev) { set_error("%s: the new states need an array of their own (the neighbours read the old ones)", who); return EXA_ERR_INVALID; }
+    if (p->mode == EXA_FV_RUSANOV && !(h > 0.0)) { set_error("%s: EXA_FV_RUSANOV needs the volume size h > 0", who); return EXA_ERR_INVALID; }
+    FvGridArgs ga{QNext_dev, nullptr, {1, 1, 1}, lambda_next_dev, {0, 0, 0, 0, 0, 0}};
+    bool bounded = false;
+    for (int f = 0; face_kind && f < 2 * p->dim; f++) {
+        if (face_kind[f] < EXA_FV_FACE_PERIODIC || face_kind[f] > EXA_FV_FACE_MIRROR) {
+            set_error("%s: face_kind[%d] = %d is none of EXA_FV_FACE_PERIODIC / _STATE / _MIRROR", who, f, face_kind[f]);
+            return EXA_ERR_INVALID;
+        }
+        ga.bkind[f] = face_kind[f];
+        bounded = bounded || face_kind[f] != EXA_FV_FACE_PERIODIC;
+    }
+    if (bounded && !face_data_dev) { set_error("%s: a face that is not periodic needs face_data_dev", who); return EXA_ERR_INVALID; }
+    ga.bstate = bounded ? face_data_dev : nullptr;                 // (null: the kernels take every face as periodic)
     long n = 1;
     for (int a = 0; a < p->dim; a++) {
-        if (grid[a] < 1 || grid[a] > 0x7fffffffL) { set_error("exa_fv_grid_step_device: grid[%d] = %ld", a, grid[a]); return EXA_ERR_INVALID; }
+        if (grid[a] < 1 || grid[a] > 0x7fffffffL) { set_error("%s: grid[%d] = %ld", who, a, grid[a]); return EXA_ERR_INVALID; }
         ga.g[a] = (int)grid[a];
         n *= grid[a];
     }
-    if (n != p->n_patches) { set_error("exa_fv_grid_step_device: the grid has %ld patches, the plan %ld", n, p->n_patches); return EXA_ERR_INVALID; }
+    if (n != p->n_patches) { set_error("%s: the grid has %ld patches, the plan %ld", who, n, p->n_patches); return EXA_ERR_INVALID; }
     // (the kernels decode a patch's grid coordinates in 32-bit arithmetic: fv_grid_coords)
-    if (n > 0xffffffffL) { set_error("exa_fv_grid_step_device: %ld patches -- a grid holds at most 2^32 - 1", n); return EXA_ERR_INVALID; }
-    if (p->H > p->P) { set_error("exa_fv_grid_step_device: halo_size %d exceeds patch_size %d (the halo would reach past the face neighbour)", p->H, p->P); return EXA_ERR_INVALID; }
+    if (n > 0xffffffffL) { set_error("%s: %ld patches -- a grid holds at most 2^32 - 1", who, n); return EXA_ERR_INVALID; }
+    if (p->H > p->P) { set_error("%s: halo_size %d exceeds patch_size %d (the halo would reach past the face neighbour)", who, p->H, p->P); return EXA_ERR_INVALID; }
     int rc = use_device(p->device);
     if (rc) return rc;
     return fv_launch(p->mode, p->dim, p->P, p->H, p->n_real, p->n_aux, p->n_patches, p->pde, const_cast<double*>(Q_dev), dt, h, nullptr,
                      (hipStream_t)stream, nullptr, centre_dev, t, &ga);
+}
+
+int exa_fv_grid_step_device_bc(exa_fv_plan* p, const double* Q_dev, double* QNext_dev, const long* grid, const int* face_kind, const double* face_data_dev,
+                               const double* centre_dev, double t, double dt, double h, double* lambda_next_dev, void* stream) {
+    return fv_grid_step("exa_fv_grid_step_device_bc", p, Q_dev, QNext_dev, grid, face_kind, face_data_dev, centre_dev, t, dt, h, lambda_next_dev, stream);
+}
+
+int exa_fv_grid_step_device(exa_fv_plan* p, const double* Q_dev, double* QNext_dev, const long* grid, const double* boundary_dev,
+                            const double* centre_dev, double t, double dt, double h, double* lambda_next_dev, void* stream) {
+    // every face periodic (boundary_dev NULL), or every face a prescribed state
+    static const int all_state[6] = {EXA_FV_FACE_STATE, EXA_FV_FACE_STATE, EXA_FV_FACE_STATE, EXA_FV_FACE_STATE, EXA_FV_FACE_STATE, EXA_FV_FACE_STATE};
+    return fv_grid_step("exa_fv_grid_step_device", p, Q_dev, QNext_dev, grid, boundary_dev ? all_state : nullptr, boundary_dev, centre_dev, t, dt, h, lambda_next_dev,
+                                      stream);
 }
 
 int exa_fv_max_eigenvalue(exa_fv_plan* p, const double* Q_dev, int halo_less, const double* centre_dev, double t, double h, double* lambda_dev,

@@ -80,12 +80,16 @@ const DgLaunchTable* dg_launch_table(int dim, int pde);
 // slot: nullptr, or one entry per patch (< 0: patch not in use, left untouched)
 // out != nullptr: out of place (QOut halo-less, [patch][P^dim][n_real + n_aux]); centre: [patch][dim] cell centres or nullptr; t: time
 // grid != nullptr: the GRID step -- the patches are the cells of a Cartesian grid g[0] x g[1] (x g[2]) (row-major), halo states are taken from the
-// face neighbours' interiors (or bstate[(axis * 2 + side) * V ..] on a domain face; null = periodic), results go to grid->out (layout of Q)
+// face neighbours' interiors (periodic wrap), results go to grid->out (layout of Q).  bstate == null: every domain face is periodic; else the face
+// (axis, side) is of kind bkind[axis * 2 + side] with its V doubles of data in bstate[(axis * 2 + side) * V ..]: EXA_FV_FACE_PERIODIC (data unused),
+// _STATE (the prescribed state beyond the face) or _MIRROR (the patch's own interior layers reflected at the face, every variable times its sign)
+constexpr int FV_FACE_PERIODIC = 0, FV_FACE_STATE = 1, FV_FACE_MIRROR = 2;
 struct FvGridArgs {
     double* out;
     const double* bstate;
     int g[3];
     double* lam;          // optional: receives the largest eigenvalue of the NEW interior states (zeroed by fv_launch on the stream)
+    int bkind[6];
 };
 int fv_launch(int mode, int dim, int P, int H, int n_real, int n_aux, long n_patches, int pde, double* Q, double dt,
               double h, const long* slot, hipStream_t s, double* out = nullptr, const double* centre = nullptr, double t = 0.0,

@@ -45,13 +45,26 @@ struct FvCellData {
     // GRID step (exa_fv_grid_step_device; the enclave task's halo fill folded into the patch update): the patches are the cells of a Cartesian
     // grid g[0] x g[1] (x g[2]), patch index row-major, and BOTH arrays are halo-less -- Q [patch][P^dim][V] is only read, `out` (same layout)
     // receives the new states.  What the stencil needs beyond a patch face comes from the adjacent interior layers of the face neighbour
-    // (periodic wrap) or, on a domain face of a non-periodic grid, is the prescribed state bstate[(axis * 2 + side) * V ..].
-    const double* bstate;     // null: periodic
+    // (periodic wrap) or, on a domain face (axis, side) that is not periodic, follows the face's kind bkind[axis * 2 + side] and its V doubles
+    // bstate[(axis * 2 + side) * V ..]: FV_FACE_STATE -- that prescribed state; FV_FACE_MIRROR -- the patch's OWN interior volume at the same
+    // distance inside the face (co[a] -> 2 H - 1 - co[a] low, 2 (P + H) - 1 - co[a] high), every variable times its sign (the doubles: +-1).
+    const double* bstate;     // null: every face periodic
     int g[3];
     double* lam;              // grid step, optional: lam[0] = max(lam[0], largest eigenvalue of the NEW interior states over the directions) -- the
                               // CFL scan of the next step without a pass of its own (integer atomic max: zeroed by the launcher)
     int grid_on;
+    int bkind[6];             // launch-uniform: read through fv_face_bits (scalar registers), never indexed by a lane
 };
+// the kinds of the 2 DIM domain faces, two bits per face; 0: every face periodic
+__device__ inline unsigned fv_face_bits(const FvCellData& cd) {
+    if (!cd.bstate) return 0u;
+    return (unsigned)cd.bkind[0] | ((unsigned)cd.bkind[1] << 2) | ((unsigned)cd.bkind[2] << 4) | ((unsigned)cd.bkind[3] << 6) | ((unsigned)cd.bkind[4] << 8) |
+           ((unsigned)cd.bkind[5] << 10);
+}
+// kind of the domain face (a, side) for a patch that lies on it (pga: its grid coordinate along a), FV_FACE_PERIODIC for every other patch
+__device__ inline int fv_face_kind(const FvCellData& cd, unsigned bits, int pga, int a, int side) {
+    return (side == 0 ? pga == 0 : pga == cd.g[a] - 1) ? (int)((bits >> (2 * (a * 2 + side))) & 3u) : FV_FACE_PERIODIC;
+}
 // logical block of workgroup b when each of the 8 XCDs (which take the workgroups of a launch round-robin) is to work on a contiguous range
 __device__ inline long fv_xcd_contiguous(long b, long n) {
     const long per = n / 8;
@@ -74,29 +87,67 @@ __device__ inline void fv_grid_coords(const FvCellData& cd, long patch, int* pg)
     pg[1] = (int)(r % (unsigned)cd.g[1]);
     pg[0] = (int)(r / (unsigned)cd.g[1]);
 }
-template <int DIM>
-__device__ inline bool fv_grid_locate(const FvCellData& cd, const int* pgc, const int* co, int a, int P, int H, long& np, int* cn) {
-    int pg[3] = {pgc[0], pgc[1], pgc[2]};
+// -> the kind of what lies there: FV_FACE_STATE: np = the face; FV_FACE_PERIODIC / FV_FACE_MIRROR: np, cn = patch and volume (coordinates with halo) whose
+// state it takes -- the face neighbour's, or (mirror) the patch's own, reflected at the face
+// (MIR: the faces have kinds of their own, a mirror among them or not; the kernels are built with and without, and a launch whose faces are all
+// periodic or all prescribed states -- the only ones there were -- runs the code it always ran)
+template <int DIM, bool MIR>
+__device__ inline int fv_grid_locate(const FvCellData& cd, const int* pgc, const int* co, int a, int P, int H, long& np, int* cn) {
     const int side = co[a] < H ? 0 : 1;
-    if (cd.bstate && (side == 0 ? pg[a] == 0 : pg[a] == cd.g[a] - 1)) { np = a * 2 + side; return true; }    // domain face: the prescribed state
-    pg[a] += side == 0 ? -1 : 1;
-    if (pg[a] < 0) pg[a] += cd.g[a];
-    if (pg[a] >= cd.g[a]) pg[a] -= cd.g[a];
-    np = DIM == 3 ? ((long)pg[0] * cd.g[1] + pg[1]) * cd.g[2] + pg[2] : (long)pg[0] * cd.g[1] + pg[1];
+    if constexpr (!MIR) {                                             // every domain face is periodic (no table) or a prescribed state
+        int pg[3] = {pgc[0], pgc[1], pgc[2]};
+        if (cd.bstate && (side == 0 ? pg[a] == 0 : pg[a] == cd.g[a] - 1)) { np = a * 2 + side; return FV_FACE_STATE; }
+        pg[a] += side == 0 ? -1 : 1;
+        if (pg[a] < 0) pg[a] += cd.g[a];
+        if (pg[a] >= cd.g[a]) pg[a] -= cd.g[a];
+        np = DIM == 3 ? ((long)pg[0] * cd.g[1] + pg[1]) * cd.g[2] + pg[2] : (long)pg[0] * cd.g[1] + pg[1];
 #pragma unroll
-    for (int b = 0; b < DIM; b++) cn[b] = b == a ? (side == 0 ? co[b] + P : co[b] - P) : co[b];     // the interior volume it mirrors
-    return false;
+        for (int b = 0; b < DIM; b++) cn[b] = b == a ? (side == 0 ? co[b] + P : co[b] - P) : co[b];     // the interior volume it mirrors
+        return FV_FACE_PERIODIC;
+    }
+    const int kind = fv_face_kind(cd, fv_face_bits(cd), pgc[a], a, side);
+    if (kind == FV_FACE_STATE) { np = a * 2 + side; return kind; }    // domain face: the prescribed state
+    const bool own = kind == FV_FACE_MIRROR;
+    int na = pgc[a];                                                  // (no private array indexed by a: selects)
+    if (!own) {
+        na += side == 0 ? -1 : 1;
+        if (na < 0) na += cd.g[a];
+        if (na >= cd.g[a]) na -= cd.g[a];
+    }
+    const int p0 = a == 0 ? na : pgc[0], p1 = a == 1 ? na : pgc[1], p2 = a == 2 ? na : pgc[2];
+    np = DIM == 3 ? ((long)p0 * cd.g[1] + p1) * cd.g[2] + p2 : (long)p0 * cd.g[1] + p1;
+#pragma unroll
+    for (int b = 0; b < DIM; b++) {
+        if (b != a) cn[b] = co[b];
+        else if (own) cn[b] = (side == 0 ? 2 * H - 1 : 2 * (P + H) - 1) - co[b];
+        else cn[b] = side == 0 ? co[b] + P : co[b] - P;                  // the interior volume it mirrors
+    }
+    return own ? FV_FACE_MIRROR : FV_FACE_PERIODIC;
 }
-// ... as an address in the halo-less array Q [patch][P^DIM][V]
-template <int DIM>
-__device__ inline const double* fv_grid_source(const double* Q, const FvCellData& cd, const int* pgc, const int* co, int a, int P, int H, int V) {
+// ... as an address in the halo-less array Q [patch][P^DIM][V].  sgn (optional): receives the V signs of a mirror face, null for the other kinds
+template <int DIM, bool MIR>
+__device__ inline const double* fv_grid_source(const double* Q, const FvCellData& cd, const int* pgc, const int* co, int a, int P, int H, int V,
+                                               const double** sgn = nullptr) {
     long np;
     int cn[3];
-    if (fv_grid_locate<DIM>(cd, pgc, co, a, P, H, np, cn)) return cd.bstate + np * V;
+    const int kind = fv_grid_locate<DIM, MIR>(cd, pgc, co, a, P, H, np, cn);
+    if (sgn) *sgn = kind == FV_FACE_MIRROR ? cd.bstate + (a * 2 + (co[a] < H ? 0 : 1)) * V : nullptr;
+    if (kind == FV_FACE_STATE) return cd.bstate + np * V;
     long c = 0;
 #pragma unroll
     for (int b = 0; b < DIM; b++) c = c * P + (cn[b] - H);
     return Q + (np * (DIM == 3 ? (long)P * P * P : (long)P * P) + c) * V;
+}
+// ... as the value of variable v
+template <int DIM, bool MIR>
+__device__ inline double fv_grid_value(const double* Q, const FvCellData& cd, const int* pgc, const int* co, int a, int P, int H, int V, int v) {
+    if constexpr (MIR) {
+        const double* sg = nullptr;
+        const double x = fv_grid_source<DIM, true>(Q, cd, pgc, co, a, P, H, V, &sg)[v];
+        return sg ? x * sg[v] : x;
+    } else {
+        return fv_grid_source<DIM, false>(Q, cd, pgc, co, a, P, H, V)[v];
+    }
 }
 // the e-th face-halo volume of a patch (e < 2 * DIM * H * P^(DIM-1); corners and edges are not part of the 2 DIM + 1-point stencil):
 // coordinates with halo and the axis it lies beyond
@@ -151,7 +202,7 @@ constexpr int FV_HR = 16;          // double2 per thread that hold a block in fl
 #ifndef EXA_FV_GRID_WAVES
 #define EXA_FV_GRID_WAVES 1          // persistent grid step: no register cap (199 VGPRs, two workgroups per CU: 0.855 ms per 2^20-patch step); capped at 168 for
 #endif                               // three workgroups per CU it spills 31 registers and takes 0.995 ms
-template <int DIM, class PDE, int MODE, int CPT, int NT, bool STAGE, class SHAPE = FvRuntimeShape, bool PERSIST = false, bool GRID = false>
+template <int DIM, class PDE, int MODE, int CPT, int NT, bool STAGE, class SHAPE = FvRuntimeShape, bool PERSIST = false, bool GRID = false, bool MIR = false>
 __global__ void __launch_bounds__(NT, ((GRID && PERSIST && NT == 256) ? EXA_FV_GRID_WAVES : 1))
 fv_rusanov_kernel(double* __restrict__ Q, int P_rt, int H_rt, int m_rt, int V_rt, double dt, double dt_over_h, long n_patches,
                   int ppb, const long* __restrict__ slot, FvCellData cd) {
@@ -173,6 +224,10 @@ fv_rusanov_kernel(double* __restrict__ Q, int P_rt, int H_rt, int m_rt, int V_rt
     constexpr int HRS = !PERSIST ? 1 : (SHAPE::P ? ((NT / PPOW) * (GRID ? PPOW : SPOW) * SHAPE::V / 2 + NT - 1) / NT : FV_HR);
     v2d hold[HRS];
     const long gvol = GRID ? (long)ncell : vol;                   // volumes per patch in the array Q (grid step: halo-less)
+    // grid step: kinds of the domain faces (launch-uniform); mir: the faces have kinds of their own (the dispatch launches the MIR build for such a grid only)
+    static_assert(GRID || !MIR, "mirror faces belong to the grid step");
+    [[maybe_unused]] const unsigned fbits = GRID ? fv_face_bits(cd) : 0u;
+    constexpr bool mir = MIR;
     auto request = [&](long blk) {                                // block blk -> registers (PERSIST: Q 16-byte aligned, even block size)
         const long first = blk * ppb;
         const long npatch = (n_patches - first < ppb) ? n_patches - first : ppb;
@@ -252,7 +307,7 @@ fv_rusanov_kernel(double* __restrict__ Q, int P_rt, int H_rt, int m_rt, int V_rt
             int pp, hv, v, co[3] = {0, 0, 0}, ax;
             remote_elem(npatch, e, pp, hv, v);
             halo_place(pp, hv, co, ax);
-            hg[r] = fv_grid_source<DIM>(Q, cd, pgtab + (half * ppb + pp) * 3, co, ax, P, H, V)[v];
+            hg[r] = fv_grid_value<DIM, MIR>(Q, cd, pgtab + (half * ppb + pp) * 3, co, ax, P, H, V, v);
         }
     };
     [[maybe_unused]] auto gather_land_any = [&](long blk, int half) {
@@ -272,7 +327,7 @@ fv_rusanov_kernel(double* __restrict__ Q, int P_rt, int H_rt, int m_rt, int V_rt
             int pp, hv, v, co[3] = {0, 0, 0}, ax;
             remote_elem(npatch, e, pp, hv, v);
             const int off = halo_place(pp, hv, co, ax);
-            fv_lds[off + v] = fv_grid_source<DIM>(Q, cd, pgtab + (half * ppb + pp) * 3, co, ax, P, H, V)[v];
+            fv_lds[off + v] = fv_grid_value<DIM, MIR>(Q, cd, pgtab + (half * ppb + pp) * 3, co, ax, P, H, V, v);
         }
     };
     // FULL blocks (ppb patches): which remote states a lane fetches, where they come from inside the neighbour patch and where they land in the LDS
@@ -298,22 +353,42 @@ fv_rusanov_kernel(double* __restrict__ Q, int P_rt, int H_rt, int m_rt, int V_rt
             int cg = 0;
 #pragma unroll
             for (int b = 0; b < DIM; b++) cg = cg * P + ((b == ax ? (side == 0 ? co[b] + P : co[b] - P) : co[b]) - H);
+            // (mirror face: the patch's own volume at the same distance inside the face lies `dl` volumes along ax from the one a neighbour
+            // would supply; kept in the bits above the face number)
+            const int layer = side == 0 ? co[ax] : co[ax] - P - H;
+            const int dl = side == 0 ? 2 * H - 1 - 2 * layer - P : P - 1 - 2 * layer;
             g_pp[r] = pp;
-            g_face[r] = ax * 2 + side;
+            g_face[r] = (mir ? dl * 8 : 0) + (ax * 2 + side);
             g_src[r] = cg * V + v;
             g_lds[r] = u0 < nu ? off + v : -1;
         }
     }
     [[maybe_unused]] auto unit_src = [&](int r, int half) -> const double* {
         const int* pgc = pgtab + (half * ppb + g_pp[r]) * 3;
-        const int ax = g_face[r] >> 1, side = g_face[r] & 1;
-        int pg[3] = {pgc[0], pgc[1], pgc[2]};
-        if (cd.bstate && (side == 0 ? pg[ax] == 0 : pg[ax] == cd.g[ax] - 1)) return cd.bstate + (long)g_face[r] * V + (g_src[r] % V);
-        pg[ax] += side == 0 ? -1 : 1;
-        if (pg[ax] < 0) pg[ax] += cd.g[ax];
-        if (pg[ax] >= cd.g[ax]) pg[ax] -= cd.g[ax];
-        const long np = DIM == 3 ? ((long)pg[0] * cd.g[1] + pg[1]) * cd.g[2] + pg[2] : (long)pg[0] * cd.g[1] + pg[1];
-        return Q + np * ncell * V + g_src[r];
+        if constexpr (!mir) {
+            const int ax = g_face[r] >> 1, side = g_face[r] & 1;
+            int pg[3] = {pgc[0], pgc[1], pgc[2]};
+            if (cd.bstate && (side == 0 ? pg[ax] == 0 : pg[ax] == cd.g[ax] - 1)) return cd.bstate + (long)g_face[r] * V + (g_src[r] % V);
+            pg[ax] += side == 0 ? -1 : 1;
+            if (pg[ax] < 0) pg[ax] += cd.g[ax];
+            if (pg[ax] >= cd.g[ax]) pg[ax] -= cd.g[ax];
+            const long np = DIM == 3 ? ((long)pg[0] * cd.g[1] + pg[1]) * cd.g[2] + pg[2] : (long)pg[0] * cd.g[1] + pg[1];
+            return Q + np * ncell * V + g_src[r];
+        }
+        const int face = g_face[r] & 7, ax = face >> 1, side = face & 1;
+        const int kind = fv_face_kind(cd, fbits, pgc[ax], ax, side);
+        if (kind == FV_FACE_STATE) return cd.bstate + (long)face * V + (g_src[r] % V);
+        int na = pgc[ax], shift = 0;
+        if (mir && kind == FV_FACE_MIRROR)                            // the patch itself, the reflected layer
+            shift = (g_face[r] >> 3) * (DIM == 3 ? (ax == 0 ? P * P : (ax == 1 ? P : 1)) : (ax == 0 ? P : 1)) * V;
+        else {
+            na += side == 0 ? -1 : 1;
+            if (na < 0) na += cd.g[ax];
+            if (na >= cd.g[ax]) na -= cd.g[ax];
+        }
+        const int p0 = ax == 0 ? na : pgc[0], p1 = ax == 1 ? na : pgc[1], p2 = ax == 2 ? na : pgc[2];
+        const long np = DIM == 3 ? ((long)p0 * cd.g[1] + p1) * cd.g[2] + p2 : (long)p0 * cd.g[1] + p1;
+        return Q + np * ncell * V + (g_src[r] + shift);
     };
     [[maybe_unused]] auto gather_request = [&](long blk, int half) {
         if (!fastpath || n_patches - blk * ppb < ppb) { gather_request_any(blk, half); return; }      // (misaligned arrays; ragged last block)
@@ -331,6 +406,17 @@ fv_rusanov_kernel(double* __restrict__ Q, int P_rt, int H_rt, int m_rt, int V_rt
     };
     [[maybe_unused]] auto gather_land = [&](long blk, int half) {
         if (!fastpath || n_patches - blk * ppb < ppb) { gather_land_any(blk, half); return; }
+        if constexpr (mir) {                                          // the signs of the mirror faces, where the values land
+#pragma unroll
+            for (int r = 0; r < HG2; r++) {
+                const int face = g_face[r] & 7;
+                if (fv_face_kind(cd, fbits, pgtab[(half * ppb + g_pp[r]) * 3 + (face >> 1)], face >> 1, face & 1) == FV_FACE_MIRROR) {
+                    const double* sg = cd.bstate + face * V + (g_src[r] % V);
+#pragma unroll
+                    for (int w = 0; w < GWC; w++) hg[GWC * r + w] *= sg[w];
+                }
+            }
+        }
 #pragma unroll
         for (int r = 0; r < HG2; r++) {
             if (g_lds[r] >= 0) {
@@ -352,14 +438,20 @@ fv_rusanov_kernel(double* __restrict__ Q, int P_rt, int H_rt, int m_rt, int V_rt
             long np;
             int cn[3] = {0, 0, 0};
             const double* src;
-            if (fv_grid_locate<DIM>(cd, pgtab + (half * ppb + pp) * 3, co, ax, P, H, np, cn)) src = cd.bstate + np * V;
-            else {
+            const int kind = fv_grid_locate<DIM, MIR>(cd, pgtab + (half * ppb + pp) * 3, co, ax, P, H, np, cn);
+            if (kind == FV_FACE_STATE) src = cd.bstate + np * V;
+            else {                                                    // (a mirror face: np is the patch itself, in this LDS copy)
                 long cl = 0, cg = 0;
 #pragma unroll
                 for (int b = 0; b < DIM; b++) { cl = cl * S + cn[b]; cg = cg * P + (cn[b] - H); }
                 src = (np >= first && np < first + npatch) ? fv_lds + ((np - first) * vol + cl) * V : Q + (np * ncell + cg) * V;
             }
-            for (int v = 0; v < V; v++) dst[v] = src[v];
+            if (kind == FV_FACE_MIRROR) {
+                const double* sg = cd.bstate + (ax * 2 + (co[ax] < H ? 0 : 1)) * V;
+                for (int v = 0; v < V; v++) dst[v] = src[v] * sg[v];
+            } else {
+                for (int v = 0; v < V; v++) dst[v] = src[v];
+            }
         }
     };
     if constexpr (PERSIST) request(blockIdx.x);
@@ -473,18 +565,25 @@ fv_rusanov_kernel(double* __restrict__ Q, int P_rt, int H_rt, int m_rt, int V_rt
         const long c = BARE ? (long)id : co[0] * st[0] + co[1] * st[1] + co[2] * st[2];
         cidx[k] = c;
         // state of the volume next to c along d (BARE: across a patch face it lives in the neighbour patch)
-        auto nbr = [&](int d, int sgn) -> const double* {
+        // (sg: receives the signs of a mirror face the neighbour lies beyond, else null)
+        auto nbr = [&](int d, int sgn, [[maybe_unused]] const double** sg) -> const double* {
             if constexpr (BARE) {
                 if (sgn < 0 ? co[d] - 1 < H : co[d] + 1 >= P + H) {
                     int cn[3] = {co[0], co[1], co[2]}, pgc[3];
                     cn[d] += sgn;
                     fv_grid_coords<DIM>(cd, patch, pgc);
-                    return fv_grid_source<DIM>(Q, cd, pgc, cn, d, P, H, V);
+                    return fv_grid_source<DIM, MIR>(Q, cd, pgc, cn, d, P, H, V, mir ? sg : nullptr);
                 }
                 const long ds = DIM == 3 ? (d == 0 ? (long)P * P : (d == 1 ? P : 1)) : (d == 0 ? P : 1);
                 return Qp + (c + sgn * ds) * V;
             }
             return Qp + (c + sgn * st[d]) * V;
+        };
+        // a neighbour beyond a mirror face: its evolved variables times the face's signs
+        [[maybe_unused]] auto nbr_sign = [&](const double* sg, double (&q)[MAXV]) {
+#pragma unroll
+            for (int v = 0; v < MAXV; v++)
+                if (sg && v < m) q[v] *= sg[v];
         };
         // centre of the volume (exahype2::fv::getVolumeCentre: patch centre - half the patch + (index + 1/2) h) and of its 2 dim neighbours
         [[maybe_unused]] double xc[3] = {0.0, 0.0, 0.0};
@@ -512,12 +611,14 @@ fv_rusanov_kernel(double* __restrict__ Q, int P_rt, int H_rt, int m_rt, int V_rt
 #pragma unroll
                 for (int v = 0; v < MAXV; v++) { Fp[v] = 0.0; Fm[v] = 0.0; }
                 double qP[MAXV], qM[MAXV];
-                const double *pP = nbr(d, 1), *pM = nbr(d, -1);
+                [[maybe_unused]] const double *sP = nullptr, *sM = nullptr;
+                const double *pP = nbr(d, 1, &sP), *pM = nbr(d, -1, &sM);
 #pragma unroll
                 for (int v = 0; v < MAXV; v++) {
                     qP[v] = v < m ? pP[v] : 0.0;
                     qM[v] = v < m ? pM[v] : 0.0;
                 }
+                if constexpr (BARE && mir) { nbr_sign(sP, qP); nbr_sign(sM, qM); }
                 [[maybe_unused]] double xp[3], xm[3];
                 if constexpr (pde_has_xt<PDE>::value) { shifted(d, 1.0, xp); shifted(d, -1.0, xm); }
                 if (co[d] + 1 < P + H) fv_flux<PDE>(qP, xp, cd.t, d, Fp);
@@ -529,12 +630,14 @@ fv_rusanov_kernel(double* __restrict__ Q, int P_rt, int H_rt, int m_rt, int V_rt
 #pragma unroll
             for (int d = 0; d < DIM; d++) {
                 double qP[MAXV], qM[MAXV];
-                const double *pP = nbr(d, 1), *pM = nbr(d, -1);
+                [[maybe_unused]] const double *sP = nullptr, *sM = nullptr;
+                const double *pP = nbr(d, 1, &sP), *pM = nbr(d, -1, &sM);
 #pragma unroll
                 for (int v = 0; v < MAXV; v++) {
                     qP[v] = v < m ? pP[v] : 0.0;
                     qM[v] = v < m ? pM[v] : 0.0;
                 }
+                if constexpr (BARE && mir) { nbr_sign(sP, qP); nbr_sign(sM, qM); }
                 [[maybe_unused]] double xp[3], xm[3];
                 if constexpr (pde_has_xt<PDE>::value) { shifted(d, 1.0, xp); shifted(d, -1.0, xm); }
                 const double lc = fv_eig<PDE>(qc, xc, cd.t, d);
@@ -554,12 +657,14 @@ fv_rusanov_kernel(double* __restrict__ Q, int P_rt, int H_rt, int m_rt, int V_rt
 #pragma unroll
             for (int d = 0; d < DIM; d++) {
                 double qpp[MAXV], qmp[MAXV];
-                const double *pP = nbr(d, 1), *pM = nbr(d, -1);
+                [[maybe_unused]] const double *sP = nullptr, *sM = nullptr;
+                const double *pP = nbr(d, 1, &sP), *pM = nbr(d, -1, &sM);
 #pragma unroll
                 for (int v = 0; v < MAXV; v++) {
                     qpp[v] = v < m ? pP[v] : 0.0;
                     qmp[v] = v < m ? pM[v] : 0.0;
                 }
+                if constexpr (BARE && mir) { nbr_sign(sP, qpp); nbr_sign(sM, qmp); }
                 const double* qcp = qc;
                 [[maybe_unused]] double xp[3], xm[3];
                 if constexpr (pde_has_xt<PDE>::value) { shifted(d, 1.0, xp); shifted(d, -1.0, xm); }
@@ -760,7 +865,7 @@ __host__ __device__ constexpr size_t slab_lds_bytes(int S, int V, bool cache) {
 // halo-fill pass, no halo bytes in HBM at all: 2 P^3 V doubles per patch and step + the neighbours' boundary layers (which their own
 // workgroups read anyway).
 constexpr int SLAB_NH = 2;          // doubles per thread that hold the in-plane face-halo values of a plane in flight (grid step: 4 H P V <= 512)
-template <class PDE, int MODE, bool CACHE, bool FITNV = false, bool GRID = false>
+template <class PDE, int MODE, bool CACHE, bool FITNV = false, bool GRID = false, bool MIR = false>
 __global__ void __launch_bounds__(SLAB_NT, 2)
 fv_rusanov_slab_kernel(double* __restrict__ Q, int P, int H, int m, int V, double dt, double dt_over_h,
                        const long* __restrict__ slot, FvCellData cd) {
@@ -792,16 +897,22 @@ fv_rusanov_slab_kernel(double* __restrict__ Q, int P, int H, int m, int V, doubl
     const int x = cell_ok ? j * S + k : ((((tid >> 5) << 1) < P ? ((tid >> 5) << 1) : 0) + H) * S + H;
     const int par0 = (int)((reinterpret_cast<unsigned long long>(Qp) >> 3) & 1);
     // grid step: where plane i comes from -- this patch, or (i outside the interior planes) the neighbour along axis 0; a domain face of a
-    // non-periodic grid has no plane: its ring slot is filled with the prescribed state
+    // non-periodic grid has no plane: its ring slot is filled with the prescribed state (bnd_*) -- or, a mirror face (mir_*), takes the patch's own
+    // plane at the same distance inside the face, every variable times its sign
     [[maybe_unused]] const double* nb_lo = Qp;
     [[maybe_unused]] const double* nb_hi = Qp;
-    [[maybe_unused]] bool bnd_lo = false, bnd_hi = false;
+    [[maybe_unused]] bool bnd_lo = false, bnd_hi = false, mir_lo = false, mir_hi = false;
+    [[maybe_unused]] const unsigned fbits = GRID ? fv_face_bits(cd) : 0u;
+    constexpr bool mir = MIR;                                      // (the faces have kinds of their own: the dispatch launches this build for such a grid only)
     if constexpr (GRID) {
         const long b = patch;
         const int g0 = (int)(b / ((long)cd.g[1] * cd.g[2]));
         const long rest = b - (long)g0 * cd.g[1] * cd.g[2];
-        bnd_lo = cd.bstate && g0 == 0;
-        bnd_hi = cd.bstate && g0 == cd.g[0] - 1;
+        const int klo = g0 == 0 ? (int)(fbits & 3u) : FV_FACE_PERIODIC, khi = g0 == cd.g[0] - 1 ? (int)((fbits >> 2) & 3u) : FV_FACE_PERIODIC;
+        bnd_lo = mir ? klo == FV_FACE_STATE : (cd.bstate && g0 == 0);
+        bnd_hi = mir ? khi == FV_FACE_STATE : (cd.bstate && g0 == cd.g[0] - 1);
+        mir_lo = mir && klo == FV_FACE_MIRROR;
+        mir_hi = mir && khi == FV_FACE_MIRROR;
         const int gl = g0 == 0 ? cd.g[0] - 1 : g0 - 1, gh = g0 == cd.g[0] - 1 ? 0 : g0 + 1;
         nb_lo = Q + ((long)gl * cd.g[1] * cd.g[2] + rest) * P * dplane;
         nb_hi = Q + ((long)gh * cd.g[1] * cd.g[2] + rest) * P * dplane;
@@ -810,8 +921,8 @@ fv_rusanov_slab_kernel(double* __restrict__ Q, int P, int H, int m, int V, doubl
     // plane has no source: any valid address, its ring slot is filled with the state)
     auto plane_src = [&](int i) -> const double* {
         if constexpr (GRID) {
-            if (i < H) return bnd_lo ? Qp : nb_lo + (long)(i + P - H) * dplane;
-            if (i >= P + H) return bnd_hi ? Qp : nb_hi + (long)(i - P - H) * dplane;
+            if (i < H) return mir_lo ? Qp + (long)(H - 1 - i) * dplane : (bnd_lo ? Qp : nb_lo + (long)(i + P - H) * dplane);
+            if (i >= P + H) return mir_hi ? Qp + (long)(2 * P + H - 1 - i) * dplane : (bnd_hi ? Qp : nb_hi + (long)(i - P - H) * dplane);
             return Qp + (long)(i - H) * dplane;
         }
         return Qp + (long)i * plane;
@@ -857,6 +968,20 @@ fv_rusanov_slab_kernel(double* __restrict__ Q, int P, int H, int m, int V, doubl
                 for (int xx = tid; xx < plane; xx += SLAB_NT) dst[xx] = bs[xx % V];
                 return;
             }
+            if (mir && ((i < H && mir_lo) || (i >= P + H && mir_hi))) {     // plane beyond a mirror face: the patch's own plane, times the signs (workgroup-uniform)
+                const double* sg = cd.bstate + (i < H ? 0 : 1) * V;
+#pragma unroll
+                for (int r = 0; r < SLAB_NR; r++) {
+                    const int xx = tid + r * SLAB_NT;
+                    if (xx < npair) {
+                        dst[d2r(head + 2 * xx)] = hd[r].x * sg[(head + 2 * xx) % V];
+                        dst[d2r(head + 2 * xx + 1)] = hd[r].y * sg[(head + 2 * xx + 1) % V];
+                    }
+                }
+                if (tid == 0 && head) dst[d2r(0)] = hh * sg[0];
+                if (tid == 1 && ((n - head) & 1)) dst[d2r(n - 1)] = ht * sg[(n - 1) % V];
+                return;
+            }
 #pragma unroll
             for (int r = 0; r < SLAB_NR; r++) {                    // rows of P V doubles into rows of S V: 8-byte stores (a pair may straddle a row end)
                 const int xx = tid + r * SLAB_NT;
@@ -880,9 +1005,10 @@ fv_rusanov_slab_kernel(double* __restrict__ Q, int P, int H, int m, int V, doubl
     };
     // grid step, interior planes: the 4 H P face-halo volumes (rows j < H, j >= P + H; columns k likewise) come from the neighbours along axes 1 and 2.
     // Which entries a lane fetches is fixed for the patch: source of plane 0 (+ i planes; a boundary state does not move), place in the plane
-    [[maybe_unused]] double hval[GRID ? SLAB_NH : 1];
+    [[maybe_unused]] double hval[GRID ? SLAB_NH : 1], hsv[GRID ? SLAB_NH : 1];
     [[maybe_unused]] const double* hsrc[GRID ? SLAB_NH : 1];
     [[maybe_unused]] int hstep[GRID ? SLAB_NH : 1], hoff[GRID ? SLAB_NH : 1];
+    [[maybe_unused]] int hsgn[GRID ? SLAB_NH : 1];                 // entry of cd.bstate that holds the value's sign (a mirror face), or -1
     if constexpr (GRID) {
         const int nhe = 4 * H * P * V;
         int pgc[3];
@@ -895,10 +1021,13 @@ fv_rusanov_slab_kernel(double* __restrict__ Q, int P, int H, int m, int V, doubl
             const int layer = rr % H, t = rr / H, a = 1 + (f >> 1);
             const int edge = (f & 1) ? P + H + layer : layer;
             const int co[3] = {H, a == 1 ? edge : t + H, a == 2 ? edge : t + H};          // (first interior plane: + (i - H) halo-less planes)
-            const double* src = fv_grid_source<3>(Q, cd, pgc, co, a, P, H, V);
+            // (a mirror source lies in this patch's own planes and steps with them like a neighbour's; a prescribed state stands still)
+            const double* sg = nullptr;
+            const double* src = fv_grid_source<3, MIR>(Q, cd, pgc, co, a, P, H, V, mir ? &sg : nullptr);
             const bool fixed = cd.bstate && src >= cd.bstate && src < cd.bstate + 6 * V;
             hsrc[r] = src + v;
             hstep[r] = fixed ? 0 : dplane;
+            hsgn[r] = sg ? (int)(sg - cd.bstate) + v : -1;
             hoff[r] = e0 < nhe ? (co[1] * S + co[2]) * V + v : -1;
         }
     }
@@ -907,6 +1036,10 @@ fv_rusanov_slab_kernel(double* __restrict__ Q, int P, int H, int m, int V, doubl
             if (i >= H && i < P + H) {
 #pragma unroll
                 for (int r = 0; r < SLAB_NH; r++) hval[r] = hsrc[r][(long)(i - H) * hstep[r]];   // (unconditional: idle lanes repeat the last entry)
+                if constexpr (mir) {
+#pragma unroll
+                    for (int r = 0; r < SLAB_NH; r++) hsv[r] = hsgn[r] >= 0 ? cd.bstate[hsgn[r]] : 1.0;      // (no table is touched without a mirror entry)
+                }
             }
         }
     };
@@ -916,7 +1049,7 @@ fv_rusanov_slab_kernel(double* __restrict__ Q, int P, int H, int m, int V, doubl
                 double* dst = org(i);
 #pragma unroll
                 for (int r = 0; r < SLAB_NH; r++)
-                    if (hoff[r] >= 0) dst[hoff[r]] = hval[r];
+                    if (hoff[r] >= 0) dst[hoff[r]] = (mir && hsgn[r] >= 0) ? hval[r] * hsv[r] : hval[r];
             }
         }
     };
@@ -1259,7 +1392,7 @@ __global__ void pde_eval_kernel(int normal, long n, int stride, const double* __
     if (lam) lam[i] = fv_eig<PDE>(&Q[i * stride], x, t, normal);
 }
 
-template <int DIM, class PDE, int MODE, bool GRID>
+template <int DIM, class PDE, int MODE, bool GRID, bool MIR = false>
 static int fv_dispatch(int P, int H, int m, int V, long n_patches, double* Q, double dt, double h, const long* slot, hipStream_t s,
                        const FvCellData& cd) {
     const long ncell = (DIM == 3) ? (long)P * P * P : (long)P * P;
@@ -1288,7 +1421,7 @@ static int fv_dispatch(int P, int H, int m, int V, long n_patches, double* Q, do
                 constexpr int RNT = EXA_FV_REF_NT;
                 const int rppb = RNT / 16;
                 const size_t rlds = (size_t)rppb * pvol * V * sizeof(double) + (GRID ? (size_t)rppb * 32 : 0);
-                auto kr = fv_rusanov_kernel<DIM, PDE, MODE, 1, RNT, true, FvShape<4, 1, 5, 10>, true, GRID>;
+                auto kr = fv_rusanov_kernel<DIM, PDE, MODE, 1, RNT, true, FvShape<4, 1, 5, 10>, true, GRID, MIR>;
                 int per_cu = 0, dev = 0, cus = 0;
                 hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, reinterpret_cast<const void*>(kr), RNT, rlds);
                 hipGetDevice(&dev);
@@ -1304,36 +1437,36 @@ static int fv_dispatch(int P, int H, int m, int V, long n_patches, double* Q, do
                 }
             }
 #endif
-            auto kp = fv_rusanov_kernel<DIM, PDE, MODE, 1, 256, true, FvShape<4, 1, 5, 10>, true, GRID>;
+            auto kp = fv_rusanov_kernel<DIM, PDE, MODE, 1, 256, true, FvShape<4, 1, 5, 10>, true, GRID, MIR>;
             const unsigned pg = persist ? persist_grid(reinterpret_cast<const void*>(kp)) : 0;
             if (pg > 0) hipLaunchKernelGGL(kp, dim3(pg), dim3(256), lds, s, Q, P, H, m, V, dt, doh, n_patches, ppb, slot, cd);
-            else hipLaunchKernelGGL((fv_rusanov_kernel<DIM, PDE, MODE, 1, 256, true, FvShape<4, 1, 5, 10>, false, GRID>), grid, dim3(256), lds, s, Q, P, H, m, V, dt, doh, n_patches, ppb, slot, cd);
+            else hipLaunchKernelGGL((fv_rusanov_kernel<DIM, PDE, MODE, 1, 256, true, FvShape<4, 1, 5, 10>, false, GRID, MIR>), grid, dim3(256), lds, s, Q, P, H, m, V, dt, doh, n_patches, ppb, slot, cd);
         } else if (lds <= 64 * 1024)     // staged: several workgroups per CU keep HBM requests in flight (the persistent form
                                          // with its 64 holding VGPRs lost there: 2-D P = 16 0.55 -> 0.67 ms)
-            hipLaunchKernelGGL((fv_rusanov_kernel<DIM, PDE, MODE, 1, 256, true, FvRuntimeShape, false, GRID>), grid, dim3(256), lds, s, Q, P, H, m, V, dt, doh, n_patches, ppb, slot, cd);
+            hipLaunchKernelGGL((fv_rusanov_kernel<DIM, PDE, MODE, 1, 256, true, FvRuntimeShape, false, GRID, MIR>), grid, dim3(256), lds, s, Q, P, H, m, V, dt, doh, n_patches, ppb, slot, cd);
         else
-            hipLaunchKernelGGL((fv_rusanov_kernel<DIM, PDE, MODE, 1, 256, false, FvRuntimeShape, false, GRID>), grid, dim3(256), 0, s, Q, P, H, m, V, dt, doh, n_patches, ppb, slot, cd);
+            hipLaunchKernelGGL((fv_rusanov_kernel<DIM, PDE, MODE, 1, 256, false, FvRuntimeShape, false, GRID, MIR>), grid, dim3(256), 0, s, Q, P, H, m, V, dt, doh, n_patches, ppb, slot, cd);
     } else if (ncell <= 1024) {
         const size_t lds = (size_t)pvol * V * sizeof(double) + (GRID ? 32 : 0);
         if (lds <= 64 * 1024)
-            hipLaunchKernelGGL((fv_rusanov_kernel<DIM, PDE, MODE, 1, 1024, true, FvRuntimeShape, false, GRID>), dim3((unsigned)n_patches), dim3(1024), lds, s, Q, P, H, m, V, dt, doh, n_patches, 1, slot, cd);
+            hipLaunchKernelGGL((fv_rusanov_kernel<DIM, PDE, MODE, 1, 1024, true, FvRuntimeShape, false, GRID, MIR>), dim3((unsigned)n_patches), dim3(1024), lds, s, Q, P, H, m, V, dt, doh, n_patches, 1, slot, cd);
         else
-            hipLaunchKernelGGL((fv_rusanov_kernel<DIM, PDE, MODE, 1, 1024, false, FvRuntimeShape, false, GRID>), dim3((unsigned)n_patches), dim3(1024), 0, s, Q, P, H, m, V, dt, doh, n_patches, 1, slot, cd);
+            hipLaunchKernelGGL((fv_rusanov_kernel<DIM, PDE, MODE, 1, 1024, false, FvRuntimeShape, false, GRID, MIR>), dim3((unsigned)n_patches), dim3(1024), 0, s, Q, P, H, m, V, dt, doh, n_patches, 1, slot, cd);
     } else if (DIM == 3 && P * P <= 256 && S * S * V <= 2 * SLAB_NR * SLAB_NT && !pde_has_xt<PDE>::value && !pde_has_ncp<PDE>::value &&
                (!cd.out || GRID) && (!GRID || 4 * H * P * V <= SLAB_NH * SLAB_NT)) {
         // plane-streaming variant: 3-plane LDS ring (+ 2 planes of per-volume scalars), one workgroup per patch
         constexpr bool CACHE = (MODE == 1) && has_fv_cache<PDE>::value;
         if (CACHE && m != PDE::NV) { set_error("FV Rusanov: the PDE evolves %d variables, got n_real = %d", PDE::NV, m); return -1; }
         const size_t lds = slab_lds_bytes(S, V, CACHE);
-        auto kern = CACHE ? fv_rusanov_slab_kernel<PDE, MODE, CACHE, false, GRID>
-                          : (m == PDE::NV ? fv_rusanov_slab_kernel<PDE, MODE, false, true, GRID> : fv_rusanov_slab_kernel<PDE, MODE, false, false, GRID>);
+        auto kern = CACHE ? fv_rusanov_slab_kernel<PDE, MODE, CACHE, false, GRID, MIR>
+                          : (m == PDE::NV ? fv_rusanov_slab_kernel<PDE, MODE, false, true, GRID, MIR> : fv_rusanov_slab_kernel<PDE, MODE, false, false, GRID, MIR>);
         if (lds > 64 * 1024) {
             hipError_t ea = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
             if (ea != hipSuccess) { set_error("hipFuncSetAttribute(fv slab, %zu B LDS): %s", lds, hipGetErrorString(ea)); return -2; }
         }
         hipLaunchKernelGGL(kern, dim3((unsigned)n_patches), dim3(SLAB_NT), lds, s, Q, P, H, m, V, dt, doh, slot, cd);
     } else if (ncell <= 4096) {
-        hipLaunchKernelGGL((fv_rusanov_kernel<DIM, PDE, MODE, 4, 1024, false, FvRuntimeShape, false, GRID>), dim3((unsigned)n_patches), dim3(1024), 0, s, Q, P, H, m, V, dt, doh, n_patches, 1, slot, cd);
+        hipLaunchKernelGGL((fv_rusanov_kernel<DIM, PDE, MODE, 4, 1024, false, FvRuntimeShape, false, GRID, MIR>), dim3((unsigned)n_patches), dim3(1024), 0, s, Q, P, H, m, V, dt, doh, n_patches, 1, slot, cd);
     }
     else {
         set_error("FV patch with %ld volumes exceeds the 4096 a workgroup keeps in registers", ncell);
@@ -1347,6 +1480,10 @@ static int fv_dispatch(int P, int H, int m, int V, long n_patches, double* Q, do
 template <int DIM, class PDE>
 static int fv_mode(int mode, int P, int H, int m, int V, long n_patches, double* Q, double dt, double h, const long* slot, hipStream_t s,
                    const FvCellData& cd) {
+    // a grid whose faces are neither all periodic (no table) nor all prescribed states takes the kernels built with the per-face kinds and the
+    // mirror's code (MIR); every other launch the ones without
+    bool mirror = false;
+    for (int f = 0; f < 2 * DIM; f++) mirror = mirror || (cd.bstate && cd.bkind[f] != FV_FACE_STATE);
     if (mode == 0) {
         // the faithful mode IS the reference's statement list (test.cpp:60-95): it has no source and no non-conservative product -- a term
         // set that carries one would be integrated as a different PDE without a word
@@ -1354,6 +1491,7 @@ static int fv_mode(int mode, int P, int H, int m, int V, long n_patches, double*
             set_error("FV faithful mode (the reference's statement list) has no source / ncp term: use EXA_FV_RUSANOV for this term set");
             return -1;
         } else {
+            if (cd.grid_on && mirror) return fv_dispatch<DIM, PDE, 0, true, true>(P, H, m, V, n_patches, Q, dt, h, slot, s, cd);
             if (cd.grid_on) return fv_dispatch<DIM, PDE, 0, true>(P, H, m, V, n_patches, Q, dt, h, slot, s, cd);
             return fv_dispatch<DIM, PDE, 0, false>(P, H, m, V, n_patches, Q, dt, h, slot, s, cd);
         }
@@ -1361,6 +1499,7 @@ static int fv_mode(int mode, int P, int H, int m, int V, long n_patches, double*
     if constexpr (pde_has_xt<PDE>::value) {
         if (slot && !cd.centre) { set_error("FV Rusanov: the masked patch update of a term set whose terms depend on position / time needs the patch centres (exa_fv_time_step_device_masked_at)"); return -1; }
     }
+    if (cd.grid_on && mirror) return fv_dispatch<DIM, PDE, 1, true, true>(P, H, m, V, n_patches, Q, dt, h, slot, s, cd);
     if (cd.grid_on) return fv_dispatch<DIM, PDE, 1, true>(P, H, m, V, n_patches, Q, dt, h, slot, s, cd);
     return fv_dispatch<DIM, PDE, 1, false>(P, H, m, V, n_patches, Q, dt, h, slot, s, cd);
 }
@@ -1374,8 +1513,8 @@ extern "C" int exa_user_pde_flags() {
     return (exa::pde_has_xt<exa::UserPDE>::value ? 1 : 0) | (exa::pde_has_ncp<exa::UserPDE>::value ? 2 : 0) | (exa::pde_has_admissible<exa::UserPDE>::value ? 4 : 0);
 }
 static exa::FvCellData make_cd(double* out, const double* centre, double t, double h, const exa::FvGridArgs* grid) {
-    exa::FvCellData cd{out, centre, t, h, nullptr, {1, 1, 1}, nullptr, 0};
-    if (grid) { cd.out = grid->out; cd.bstate = grid->bstate; cd.lam = grid->lam; cd.grid_on = 1; for (int a = 0; a < 3; a++) cd.g[a] = grid->g[a]; }
+    exa::FvCellData cd{out, centre, t, h, nullptr, {1, 1, 1}, nullptr, 0, {0, 0, 0, 0, 0, 0}};
+    if (grid) { cd.out = grid->out; cd.bstate = grid->bstate; cd.lam = grid->lam; cd.grid_on = 1; for (int a = 0; a < 3; a++) cd.g[a] = grid->g[a]; for (int f = 0; f < 6; f++) cd.bkind[f] = grid->bkind[f]; }
     return cd;
 }
 extern "C" int exa_user_fv_maxeig(int dim, int P, int H, int n_real, int n_aux, long n_patches, const double* Q, double* lam, void* stream,
@@ -1427,8 +1566,8 @@ int fv_maxeig_launch(int dim, int P, int H, int n_real, int n_aux, long n_patche
 int fv_launch(int mode, int dim, int P, int H, int n_real, int n_aux, long n_patches, int pde, double* Q, double dt,
               double h, const long* slot, hipStream_t s, double* out, const double* centre, double t, const FvGridArgs* grid) {
     const int V = n_real + n_aux;
-    FvCellData cd{out, centre, t, h, nullptr, {1, 1, 1}, nullptr, 0};
-    if (grid) { cd.out = grid->out; cd.bstate = grid->bstate; cd.lam = grid->lam; cd.grid_on = 1; for (int a = 0; a < 3; a++) cd.g[a] = grid->g[a]; }
+    FvCellData cd{out, centre, t, h, nullptr, {1, 1, 1}, nullptr, 0, {0, 0, 0, 0, 0, 0}};
+    if (grid) { cd.out = grid->out; cd.bstate = grid->bstate; cd.lam = grid->lam; cd.grid_on = 1; for (int a = 0; a < 3; a++) cd.g[a] = grid->g[a]; for (int f = 0; f < 6; f++) cd.bkind[f] = grid->bkind[f]; }
     if (grid && grid->lam) {
         hipError_t e0 = hipMemsetAsync(grid->lam, 0, sizeof(double), s);
         if (e0 != hipSuccess) { set_error("memset: %s", hipGetErrorString(e0)); return -2; }

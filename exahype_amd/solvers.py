@@ -15,7 +15,7 @@ import numpy as np
 
 from . import _lib
 from ._lib import (FV_FAITHFUL, FV_RUSANOV, PDE_ADVECTION, PDE_EULER, PDE_EULER_REF2D, check, darr, larr)
-from .boundary import Dirichlet, Outflow, Wall, coefficients as _bc_coefficients, validate_boundary
+from .boundary import Dirichlet, Outflow, Wall, coefficients as _bc_coefficients, fv_faces as _fv_faces, validate_boundary
 
 
 def _torch():
@@ -821,18 +821,64 @@ def fill_halos_dirichlet(Q, grid, dim, patch_size, halo_size, boundary):
     return Q
 
 
+def fill_halos_boundary(Q, grid, dim, patch_size, halo_size, conditions):
+    """Halo fill of a Cartesian grid of patches whose domain faces carry boundary conditions -- conditions {(axis, side): Outflow() | Wall(sign) |
+    Dirichlet(state [V]) | state [V]} (exahype_amd/boundary.py; a Wall's sign covers the evolved variables, the auxiliary ones keep theirs), a face
+    that is not named is periodic.  Axis by axis, in order, over the full transverse range: first every patch's halo layers from the face
+    neighbours' interior layers (periodic wrap), then the domain faces of that axis -- the state in every volume beyond a Dirichlet face; beyond an
+    Outflow / Wall face the patch's own interior layers mirrored at the face (halo coordinate c takes 2 H - 1 - c low, 2 (P + H) - 1 - c high)
+    times the sign.  Edge / corner entries follow from that order; the 2*dim+1-point stencil never reads them.
+
+    Q: tensor (torch, any device) or numpy array [g0, g1, (g2,) S, S, (S,) V], updated in place."""
+    P, H, S = patch_size, halo_size, patch_size + 2 * halo_size
+    is_np = isinstance(Q, np.ndarray)
+    assert tuple(Q.shape[:dim]) == tuple(grid) and all(s == S for s in Q.shape[dim:2 * dim])
+
+    def host(x):
+        return np.asarray(x, dtype=np.float64) if is_np else _torch().as_tensor(np.asarray(x, dtype=np.float64), dtype=Q.dtype, device=Q.device)
+    roll = (lambda a, s, ax: np.roll(a, s, axis=ax)) if is_np else (lambda a, s, ax: a.roll(s, dims=ax))
+    flip = (lambda a, ax: np.flip(a, axis=ax)) if is_np else (lambda a, ax: a.flip(ax))
+    V = Q.shape[-1]
+    for a in range(dim):
+        at = lambda first, layers: tuple(first if x == a else (layers if x == dim + a else slice(None)) for x in range(Q.ndim))   # noqa: E731
+        every = slice(None)
+        Q[at(every, slice(0, H))] = roll(Q[at(every, slice(P, P + H))], 1, a)
+        Q[at(every, slice(P + H, S))] = roll(Q[at(every, slice(H, 2 * H))], -1, a)
+        for side in range(2):
+            bc = conditions.get((a, side))
+            if bc is None:
+                continue
+            patch = 0 if side == 0 else grid[a] - 1                  # the patches on this face (the patch axis is dropped: layers move to dim + a - 1)
+            halo = slice(0, H) if side == 0 else slice(P + H, S)
+            inner = slice(H, 2 * H) if side == 0 else slice(P, P + H)
+            if isinstance(bc, (Outflow, Wall)):
+                sign = np.ones(V)
+                if isinstance(bc, Wall):
+                    sign[:len(bc.sign)] = bc.sign
+                Q[at(patch, halo)] = flip(Q[at(patch, inner)], dim + a - 1) * host(sign)
+            else:
+                Q[at(patch, halo)] = host(bc.state if isinstance(bc, Dirichlet) else bc)
+    return Q
+
+
 class FVPatchGrid:
     """A Cartesian grid of FV patches resident in HBM, advanced by the fused Rusanov kernel -- the role of the enclave task around the
     generated `time_step` (reference `exahype/printers/CPPPrinter.py:346`; the patch loop of `Unit test/correctness_test.cpp:118-174`).
 
     The states live HALO-LESS, `self.U` [g0, g1, (g2,) P, P, (P,) V] (as Peano keeps its patches); step(dt) is ONE launch
     (`exa_fv_grid_step_device`): the patch kernel assembles the patch with halo on chip, taking the states beyond a patch face from the face
-    neighbour's interior layers (periodic wrap, or the prescribed state on a domain face with `boundary=`), and writes the new states to a
+    neighbour's interior layers (periodic wrap, or what the boundary condition of a domain face says with `boundary=`), and writes the new states to a
     second array; the two swap (`self.U` is rebound: fetch it again after a step).  No halo pass and no halo bytes in HBM.  run(t_end) takes dt
     from the CFL condition: the kernel that writes the new states reduces their eigenvalues on the way, so a step costs ONE host read of one
     double and no scan pass.  `with_halo()` materialises the reference layout with halo -- interiors + filled halo layers -- for a caller who
     wants it (output, the plain `time_step` entry points).  fused=False keeps the two-pass form on an array with halo (halo fill by torch ops,
-    then the in-place update): the comparison the tests and the benchmark use."""
+    then the in-place update): the comparison the tests and the benchmark use.
+
+    boundary: None (periodic); one state [V] for every domain face, or a dict {(axis, side): state} that names all 2 dim faces (prescribed states,
+    `exa_fv_grid_step_device`); or a dict {(axis, side): Outflow() | Wall(...) | Dirichlet(state) | state} (exahype_amd/boundary.py,
+    `exa_fv_grid_step_device_bc`), in which a face that is not named stays periodic -- the vocabulary of AderDgSolver(boundary=), so that the grid
+    can serve as the first-order run of the same bounded domain.  An Outflow / Wall ghost is the mirrored interior volume (times the wall's sign):
+    it has its twin's eigenvalue and takes no part in the CFL scan, the prescribed states do."""
 
     def __init__(self, dim, grid, patch_size, halo_size=1, n_real=5, n_aux=0, pde=PDE_EULER, mode=FV_RUSANOV,
                  length=1.0, device=0, boundary=None, origin=None, time=0.0, fused=True):
@@ -857,7 +903,18 @@ class FVPatchGrid:
         self.time = float(time)
         self.boundary = boundary                                      # None: periodic
         self._bstate = None
-        if boundary is not None:                                      # [2 dim][V]: state of the domain face (axis, side)
+        self._kinds = self._conditions = None                         # boundary conditions per face (exa_fv_grid_step_device_bc)
+        self._lam_boundary = None                                     # largest eigenvalue of the prescribed states
+        all_faces = {(a, side) for a in range(dim) for side in range(2)}
+        if isinstance(boundary, dict) and (set(boundary) != all_faces or any(isinstance(b, (Outflow, Wall, Dirichlet)) for b in boundary.values())):
+            kinds, data, self._conditions = _fv_faces(boundary, dim, n_real, n_aux, pde)
+            self._kinds = (C.c_int * (2 * dim))(*kinds)
+            if any(k != _lib.FV_FACE_PERIODIC for k in kinds):
+                self._bstate = torch.as_tensor(data).to(self.dev).contiguous()     # [2 dim][V]: state or signs of the face (axis, side)
+            st = [f for f in range(2 * dim) if kinds[f] == _lib.FV_FACE_STATE]
+            if st:
+                self._lam_boundary = max(float(np.max(pde_eval(pde, d, data[st])[1])) for d in range(dim))
+        elif boundary is not None:                                    # [2 dim][V]: state of the domain face (axis, side)
             b = np.zeros((2 * dim, V))
             for a in range(dim):
                 for side in range(2):
@@ -898,20 +955,19 @@ class FVPatchGrid:
         S = self.P + 2 * self.H
         Q = torch.zeros(self.grid + (S,) * self.dim + (self.n_real + self.n_aux,), dtype=torch.float64, device=self.dev)
         Q[self._inner()] = self.U
-        if self.boundary is None:
-            fill_halos_periodic(Q, self.grid, self.dim, self.P, self.H)
-        else:
-            fill_halos_dirichlet(Q, self.grid, self.dim, self.P, self.H, self.boundary)
-        return Q
+        return self._fill(Q)
 
     def fill_halos(self):
         """two-pass form only: the halo layers of the array with halo from the neighbours' interiors / the boundary states (torch ops)"""
-        if self.fused:
-            return
+        if not self.fused:
+            self._fill(self._Q)
+
+    def _fill(self, Q):
+        if self._conditions is not None:
+            return fill_halos_boundary(Q, self.grid, self.dim, self.P, self.H, self._conditions)
         if self.boundary is None:
-            fill_halos_periodic(self._Q, self.grid, self.dim, self.P, self.H)
-        else:
-            fill_halos_dirichlet(self._Q, self.grid, self.dim, self.P, self.H, self.boundary)
+            return fill_halos_periodic(Q, self.grid, self.dim, self.P, self.H)
+        return fill_halos_dirichlet(Q, self.grid, self.dim, self.P, self.H, self.boundary)
 
     def set_interior(self, values):
         """values: [g.., P.., V] (numpy or tensor)."""
@@ -937,7 +993,7 @@ class FVPatchGrid:
             arr = self.U if self.fused else self._Q
             check(self.lib.exa_fv_max_eigenvalue(self.kernel._plan, C.c_void_p(arr.data_ptr()), 1 if self.fused else 0,
                                                  C.c_void_p(self.centres.data_ptr()), self.time, self.h, C.c_void_p(self._lam.data_ptr()), _stream_ptr()))
-            if self._bstate is not None:
+            if self._lam_boundary is not None:
                 self._lam.clamp_(min=self._lam_boundary)
             self._lam_valid = True
         return self._lam
@@ -959,13 +1015,18 @@ class FVPatchGrid:
         torch = _torch()
         if self._U2 is None:
             self._U2 = torch.empty_like(self.U)
-        check(self.lib.exa_fv_grid_step_device(self.kernel._plan, C.c_void_p(self.U.data_ptr()), C.c_void_p(self._U2.data_ptr()), self._grid_arr,
-                                               C.c_void_p(self._bstate.data_ptr()) if self._bstate is not None else None,
-                                               C.c_void_p(self.centres.data_ptr()), self.time, dt, self.h,
-                                               C.c_void_p(self._lam_next.data_ptr()), _stream_ptr()))
+        bstate = C.c_void_p(self._bstate.data_ptr()) if self._bstate is not None else None
+        if self._kinds is not None:
+            check(self.lib.exa_fv_grid_step_device_bc(self.kernel._plan, C.c_void_p(self.U.data_ptr()), C.c_void_p(self._U2.data_ptr()), self._grid_arr,
+                                                      self._kinds, bstate, C.c_void_p(self.centres.data_ptr()), self.time, dt, self.h,
+                                                      C.c_void_p(self._lam_next.data_ptr()), _stream_ptr()))
+        else:
+            check(self.lib.exa_fv_grid_step_device(self.kernel._plan, C.c_void_p(self.U.data_ptr()), C.c_void_p(self._U2.data_ptr()), self._grid_arr,
+                                                   bstate, C.c_void_p(self.centres.data_ptr()), self.time, dt, self.h,
+                                                   C.c_void_p(self._lam_next.data_ptr()), _stream_ptr()))
         self.U, self._U2 = self._U2, self.U
         self._lam, self._lam_next = self._lam_next, self._lam         # the scan of the new states, by the kernel that wrote them
-        if self._bstate is not None:
+        if self._lam_boundary is not None:
             self._lam.clamp_(min=self._lam_boundary)
         self._lam_valid = True
         self.time += dt

@@ -138,6 +138,22 @@ long exa_fv_qout_count(const exa_fv_plan* plan);
  * the CFL scan of the NEXT step, computed on the values the kernel holds in registers instead of by a pass of its own. */
 int exa_fv_grid_step_device(exa_fv_plan* plan, const double* Q_dev, double* QNext_dev, const long* grid, const double* boundary_dev,
                             const double* centre_dev, double t, double dt, double h, double* lambda_next_dev, void* stream);
+/* ... with a kind per domain face, face_kind[axis * 2 + side] (host, 2 dim entries; NULL: every face periodic), and the face's data
+ * face_data_dev[(axis * 2 + side) * (n_real + n_aux) ..] (device; NULL only if every face is periodic):
+ *   EXA_FV_FACE_PERIODIC  the wrap neighbour's interior layers (data unused)
+ *   EXA_FV_FACE_STATE     the prescribed state (the data) in every volume beyond the face
+ *   EXA_FV_FACE_MIRROR    the patch's OWN interior volume at the same distance inside the face -- halo coordinate c along the axis takes
+ *                         2 H - 1 - c (low) or 2 (P + H) - 1 - c (high), transverse coordinates unchanged -- every variable times its sign
+ *                         (the data: +1 / -1; all +1 is an outflow face -- the Rusanov flux becomes F(q_in) -- and -1 on the normal momentum a
+ *                         reflecting wall).  The products are exact: a mirror face adds no rounding.  The signs are not checked here.
+ * exa_fv_grid_step_device is this call with every kind EXA_FV_FACE_PERIODIC (boundary_dev NULL) or every kind EXA_FV_FACE_STATE.  A kind
+ * outside 0 .. 2 and a non-periodic kind without face_data_dev are refused. */
+#define EXA_FV_FACE_PERIODIC 0
+#define EXA_FV_FACE_STATE    1
+#define EXA_FV_FACE_MIRROR   2
+int exa_fv_grid_step_device_bc(exa_fv_plan* plan, const double* Q_dev, double* QNext_dev, const long* grid, const int* face_kind,
+                               const double* face_data_dev, const double* centre_dev, double t, double dt, double h, double* lambda_next_dev,
+                               void* stream);
 /* CFL scan of a patch array: max over the INTERIOR volumes of all patches and over the directions of the largest eigenvalue -> lambda_dev[0]
  * (device memory; one reduction launch, nothing returns to the host).  halo_less != 0: Q_dev is a halo-less array (every volume counts).
  * centre_dev / t / h: for term sets whose terms depend on position / time. */

@@ -1,0 +1,309 @@
+"""FVPatchGrid with boundary conditions per domain face (Outflow / Wall / Dirichlet, exa_fv_grid_step_device_bc) on the device.
+
+(a) every GRID dispatch branch, three fused steps held to the one-step long-double bound of tests/test_fv_kernels_hp.py against the restatement of
+    tests/fv_boundary_ref.py, the fused CFL scalar to its own rounding bound (prescribed states take part, mirror ghosts do not).  Shapes: the
+    smallest grid rows of tests/fv_cases.py per branch, and for every shape without a grid extent of 1 its sibling with one patch along axis 0 -- a
+    patch with both faces on the domain boundary, of two different conditions.  Layouts: (i) wall low / outflow high on axis 0, periodic elsewhere;
+    (ii) a different condition on every face, prescribed states included; (iii) all walls.  The advection has no wall: Dirichlet / outflow.
+    On the one-patch axis only layout (ii) sets a prescribed state against a mirror (wall | Dirichlet; the advection's layout (i) too: Dirichlet |
+    outflow); layout (i) sets two mirrors with different signs against each other (wall | outflow), layout (iii) two equal ones.
+(b) the fused step is bit-equal to the two-pass form (torch halo fill, in-place update) on the same shapes; with_halo() of the fused grid holds, in
+    the halo layer next to every patch face, what the restatement pads the global array of the device's states with (tests/fv_boundary_ref.py
+    padded: a path that shares no code with the torch fill), and is the two-pass array elsewhere on the stencil's halo entries.
+(c) a wall is a mirror: the walled run is bit-equal to the left half of a periodic run on the mirrored domain.
+(d) a closed box conserves mass and energy to rounding; a constant state under outflow is a fixed point.
+(e) a generated term set (shallow water) through its side library.
+(f) the old entry is the new one with all-periodic / all-state kinds; bad arguments are refused.
+(g) examples/sod_tube_fv_walls.py at 16 patches.
+"""
+import ctypes as C
+import json
+import os
+
+import numpy as np
+import pytest
+
+from oracle import fv_reference as R
+from tests import fv_boundary_ref as B
+from tests import fv_cases as K
+
+pytestmark = pytest.mark.gpu
+LD = np.longdouble
+E, A = R.PDE_EULER, R.PDE_ADVECTION
+
+#        branch            dim  P  H  aux  grid      pde
+SHAPES = [
+    ("ref", 2, 4, 1, 5, (1, 7), E),
+    ("ref", 2, 4, 1, 5, (5, 3), E),
+    ("staged", 3, 4, 1, 0, (2, 3, 2), E),
+    ("staged", 3, 4, 1, 0, (1, 3, 2), E),
+    ("nt1024-staged", 2, 24, 1, 3, (2, 2), E),
+    ("nt1024-staged", 2, 24, 1, 3, (1, 2), E),
+    ("slab-cache", 3, 12, 1, 2, (1, 2, 1), E),
+    ("slab-cache", 3, 15, 1, 0, (3, 2, 2), E),
+    ("slab-cache", 3, 15, 1, 0, (1, 2, 1), E),
+    ("slab-generic", 3, 13, 1, 0, (2, 1, 3), A),
+    ("slab-generic", 3, 13, 1, 0, (1, 1, 2), A),
+    ("cpt4", 2, 40, 1, 0, (2, 2), E),
+    ("cpt4", 2, 40, 1, 0, (1, 2), E),
+    ("staged", 3, 6, 2, 3, (2, 2, 1), E),             # two halo layers
+    ("staged", 3, 6, 2, 3, (1, 2, 1), E),
+]
+LAYOUTS = ("wall-outflow-x", "every-face", "all-walls")
+FAMILY = {"wall-outflow-x": "benign", "every-face": "supersonic", "all-walls": "riemann"}
+
+
+def _row(shape):
+    branch, dim, P, H, n_aux, grid, pde = shape
+    return (branch, dim, P, H, 5, n_aux, int(np.prod(grid)), pde, "grid:periodic:" + "x".join(str(g) for g in grid))
+
+
+def _id(shape):
+    return K.row_id(_row(shape)).replace("grid_periodic_", "")
+
+
+for _s in SHAPES:
+    assert K.branch(*_row(_s)[1:]) == _s[0], _s
+
+
+@pytest.fixture(scope="module")
+def exa():
+    import torch
+    assert torch.cuda.is_available(), "GPU tests need a GPU"
+    from exahype_amd import solvers
+    return solvers
+
+
+def _pde(exa, pde):
+    return exa.PDE_EULER if pde == E else exa.PDE_ADVECTION
+
+
+def _boundary(exa, shape, layout):
+    """the layout's boundary dict: every axis carries two different conditions where it carries any"""
+    branch, dim, P, H, n_aux, grid, pde = shape
+    V = 5 + n_aux
+    st = K.state(FAMILY[layout], 2 * dim, dim, 1, 0, V, 977).reshape(2 * dim, V)
+    euler = pde == E
+    if layout == "wall-outflow-x":
+        return {(0, 0): exa.Wall() if euler else exa.Dirichlet(st[0]), (0, 1): exa.Outflow()}
+    if layout == "all-walls":
+        return {(a, s): exa.Wall() if euler else exa.Outflow() for a in range(dim) for s in range(2)}
+    wall = (lambda a: exa.Wall()) if euler else (lambda a: exa.Outflow())
+    faces = {(0, 0): wall(0), (0, 1): exa.Dirichlet(st[1]), (1, 0): st[2], (1, 1): exa.Outflow()}
+    if dim == 3:
+        faces.update({(2, 0): exa.Outflow(), (2, 1): wall(2) if euler else exa.Dirichlet(st[5])})
+    return faces
+
+
+def _grid(exa, shape, layout, fused=True):
+    branch, dim, P, H, n_aux, grid, pde = shape
+    V = 5 + n_aux
+    row = _row(shape)
+    U = K.row_state(row, FAMILY[layout]).reshape(grid + (P,) * dim + (V,))
+    bnd = _boundary(exa, shape, layout)
+    kinds, data = B.faces_of(bnd, dim, 5, n_aux, pde)
+    st = [f for f in range(2 * dim) if kinds[f] == B.STATE]
+    dt, _ = K.cfl_step(U, dim, pde, extra=data[st] if st else None)
+    g = exa.FVPatchGrid(dim, grid, P, H, 5, n_aux, _pde(exa, pde), exa.FV_RUSANOV, length=K.H_VOLUME * grid[0] * P, boundary=bnd, fused=fused)
+    assert abs(g.h - K.H_VOLUME) < 1e-15
+    g.set_interior(U)
+    return g, dt, kinds, data
+
+
+@pytest.mark.parametrize("layout", LAYOUTS)
+@pytest.mark.parametrize("shape", SHAPES, ids=_id)
+def test_grid_step_with_boundaries_within_bound(exa, shape, layout):
+    branch, dim, P, H, n_aux, grid, pde = shape
+    g, dt, kinds, data = _grid(exa, shape, layout)
+    prim = K.primitives(_row(shape))
+    for step in range(3):
+        before = g.interior()
+        g.step(dt)
+        after = g.interior()
+        ref = B.grid_update(before, dt, g.h, dim, 5, pde, kinds, data, prim=prim)
+        worst = R.ratio(after, ref)
+        lam_dev = g.max_eigenvalue()
+        want, eb = B.lam_reference(after, kinds, data, dim, pde, prim)
+        if eb > 0:
+            lam_ratio = float(abs(LD(lam_dev) - want) / (R.U53 * eb))
+        else:                                                   # a constant eigenvalue (advection) has no rounding at all
+            assert lam_dev == float(want), (lam_dev, float(want))
+            lam_ratio = 0.0
+        what = "%s %s step %d" % (_id(shape), layout, step)
+        print("%s: err / bound %.3f, CFL scalar %.3f of its bound" % (what, worst, lam_ratio))
+        assert worst <= 1.0, (what, worst)
+        assert np.array_equal(after[..., 5:], before[..., 5:]), what + ": auxiliary variables changed"
+        assert lam_ratio <= 1.0, (what, lam_dev, float(want), lam_ratio)
+
+
+@pytest.mark.parametrize("layout", LAYOUTS)
+@pytest.mark.parametrize("shape", SHAPES, ids=_id)
+def test_fused_step_is_the_two_pass_form(exa, shape, layout):
+    branch, dim, P, H, n_aux, grid, pde = shape
+    g, dt, kinds, data = _grid(exa, shape, layout)
+    two, _, _, _ = _grid(exa, shape, layout, fused=False)
+    # the stencil's halo entries: exactly one coordinate in a halo layer
+    S = P + 2 * H
+    co = np.indices((S,) * dim)
+    out = sum(((co[a] < H) | (co[a] >= P + H)).astype(int) for a in range(dim))
+    for step in range(3):
+        g.step(dt)
+        two.step(dt)
+        assert np.array_equal(g.interior(), two.interior()), (step, _id(shape), layout)
+    a, b = g.with_halo().cpu().numpy(), two.with_halo().cpu().numpy()
+    U = g.interior()
+    pad = B.padded(R.assemble(U, dim), dim, kinds, data)             # the layer next to the faces, by the restatement's own padding
+    cut = a[(slice(None),) * dim + (slice(H - 1, H + P + 1),) * dim]
+    for idx in np.ndindex(*grid):
+        for ax in range(dim):
+            for side in range(2):
+                sel = [slice(1, P + 1)] * dim
+                sel[ax] = 0 if side == 0 else P + 1
+                glob = [slice(1 + idx[c] * P, 1 + (idx[c] + 1) * P) for c in range(dim)]
+                glob[ax] = idx[ax] * P if side == 0 else (idx[ax] + 1) * P + 1
+                assert np.array_equal(cut[idx][tuple(sel)], pad[tuple(glob)]), (idx, ax, side)
+    assert np.array_equal(a[(slice(None),) * dim + (out == 1,)], b[(slice(None),) * dim + (out == 1,)])
+    assert np.array_equal(a[(slice(None),) * dim + (out == 0,)], b[(slice(None),) * dim + (out == 0,)])
+
+
+def _mirrored(U, dim):
+    """[g.., P.., V] -> the patches of the domain doubled along x by its mirror image (the x momentum odd)"""
+    G = R.assemble(U, dim)
+    M = np.flip(G, axis=0).copy()
+    M[..., 1] = -M[..., 1]
+    grid = (2 * U.shape[0],) + U.shape[1:dim]
+    return np.ascontiguousarray(R.cut_patches(np.concatenate([G, M], axis=0), dim, grid, U.shape[dim]))
+
+
+@pytest.mark.parametrize("dim, P, grid", [(2, 4, (3, 2)), (3, 15, (2, 1, 2))], ids=["2d-P4-g3", "3d-P15-g2"])
+def test_walls_are_a_mirror(exa, dim, P, grid):
+    U = K.state("riemann", int(np.prod(grid)), dim, P, 0, 5, 71).reshape(grid + (P,) * dim + (5,))
+    dt, _ = K.cfl_step(U, dim, E)
+    L = K.H_VOLUME * grid[0] * P
+
+    def pair():
+        w = exa.FVPatchGrid(dim, grid, P, 1, 5, 0, exa.PDE_EULER, exa.FV_RUSANOV, length=L, boundary={(0, 0): exa.Wall(), (0, 1): exa.Wall()})
+        p = exa.FVPatchGrid(dim, (2 * grid[0],) + grid[1:], P, 1, 5, 0, exa.PDE_EULER, exa.FV_RUSANOV, length=2 * L)
+        w.set_interior(U)
+        p.set_interior(_mirrored(U, dim))
+        return w, p
+    w, p = pair()
+    for step in range(3):
+        w.step(dt)
+        p.step(dt)
+        assert np.array_equal(w.interior(), p.interior()[:grid[0]]), step
+        assert np.array_equal(_mirrored(w.interior(), dim), p.interior()), step
+    w, p = pair()
+    t_end = 4.5 * dt
+    assert w.run(t_end, cfl=0.9) == p.run(t_end, cfl=0.9) >= 4
+    assert w.time == p.time and np.array_equal(w.interior(), p.interior()[:grid[0]])
+
+
+@pytest.mark.parametrize("dim, P, grid", [(2, 4, (3, 2)), (3, 15, (1, 2, 1))], ids=["2d-P4", "3d-P15"])
+def test_closed_box_conserves_mass_and_energy(exa, dim, P, grid):
+    U = K.state("riemann", int(np.prod(grid)), dim, P, 0, 5, 13).reshape(grid + (P,) * dim + (5,))
+    dt, _ = K.cfl_step(U, dim, E)
+    g = exa.FVPatchGrid(dim, grid, P, 1, 5, 0, exa.PDE_EULER, exa.FV_RUSANOV, length=K.H_VOLUME * grid[0] * P,
+                        boundary={(a, s): exa.Wall() for a in range(dim) for s in range(2)})
+    g.set_interior(U)
+    steps = 10
+    for _ in range(steps):
+        g.step(dt)
+    new = g.interior()
+    for v in (0, 4):
+        before, after, mag = np.sum(U[..., v].astype(LD)), np.sum(new[..., v].astype(LD)), np.sum(np.abs(new[..., v]).astype(LD))
+        print("variable %d: defect %.3g of its bound" % (v, float(abs(after - before) / (16 * steps * R.U53 * mag))))
+        assert abs(after - before) <= 16 * steps * R.U53 * mag, (v, float(after - before))
+
+
+@pytest.mark.parametrize("dim, P, grid", [(2, 4, (2, 2)), (3, 15, (1, 2, 1))], ids=["2d-P4", "3d-P15"])
+def test_constant_state_is_a_fixed_point_under_outflow(exa, dim, P, grid):
+    q = np.array([1.3, 0.4, -0.2, 0.1, 2.9])
+    U = np.broadcast_to(q, grid + (P,) * dim + (5,)).copy()
+    g = exa.FVPatchGrid(dim, grid, P, 1, 5, 0, exa.PDE_EULER, exa.FV_RUSANOV, length=K.H_VOLUME * grid[0] * P,
+                        boundary={(a, s): exa.Outflow() for a in range(dim) for s in range(2)})
+    g.set_interior(U)
+    host = max(exa.pde_eval(exa.PDE_EULER, d, q[None])[1][0] for d in range(dim))       # the point-wise fp64 evaluation of the same term set
+    assert g.max_eigenvalue() == host
+    for _ in range(3):
+        g.step(0.9 * K.H_VOLUME / (dim * host))
+        assert np.array_equal(g.interior(), U)
+    want, eb = B.lam_reference(U, [B.MIRROR] * (2 * dim), None, dim, E, K.primitives(("", dim, P, 1, 5, 0, int(np.prod(grid)), E, "grid:periodic:x")))
+    assert abs(LD(g.max_eigenvalue()) - want) <= R.U53 * eb
+
+
+def test_generated_term_set_with_walls(exa):
+    """shallow water (tests/user_term_sets.py swe) on a 3 x 2 grid of 4 x 4 patches: walls at the x faces (the x discharge reflects), periodic in y"""
+    from tests import fv_user_cases as UC
+    pde = UC.term_set(UC.SW)
+    tm = UC.terms(UC.SW)
+    dim, P, grid = 2, 4, (3, 2)
+    row = ("staged", UC.SW, dim, P, 1, 0, 6, "grid:periodic:3x2")
+    U = UC.row_state(row, "riemann").reshape(grid + (P, P, 3))
+    bnd = {(0, 0): exa.Wall(sign=[1, -1, 1]), (0, 1): exa.Wall(sign=[1, -1, 1])}
+    kinds, data = [B.MIRROR, B.MIRROR, B.PERIODIC, B.PERIODIC], np.array([[1.0, -1, 1], [1, -1, 1], [0, 0, 0], [0, 0, 0]])
+    dt, h = UC.cfl_step(row, U.reshape((6, P, P, 3)), None, 0.0)
+    make = lambda fused: exa.FVPatchGrid(dim, grid, P, 1, 3, 0, pde.register(), exa.FV_RUSANOV, length=h * grid[0] * P, boundary=bnd, fused=fused)   # noqa: E731
+    g, two = make(True), make(False)
+    assert list(g._kinds) == kinds and np.array_equal(g._bstate.cpu().numpy(), data)
+    g.set_interior(U)
+    two.set_interior(U)
+    for step in range(3):
+        before = g.interior()
+        g.step(dt)
+        two.step(dt)
+        after = g.interior()
+        assert np.array_equal(after, two.interior()), step
+        worst = R.ratio(after, B.user_grid_update(before, dt, g.h, dim, tm, kinds, data))
+        print("swe with walls step %d: err / bound %.3f" % (step, worst))
+        assert worst <= 1.0, (step, worst)
+
+
+def test_old_entry_is_the_new_one_and_bad_arguments_are_refused(exa):
+    import torch
+    from exahype_amd import _lib
+    lib = _lib.load()
+    dim, P, grid, V = 2, 4, (3, 2), 10
+    U = torch.as_tensor(K.state("benign", 6, dim, P, 0, V, 3)).cuda()
+    bst = torch.as_tensor(K.state("benign", 4, dim, 1, 0, V, 8).reshape(4, V)).cuda()
+    k = exa.FVRusanovKernel(dim, P, 1, 5, 5, 6, exa.PDE_EULER, exa.FV_RUSANOV)
+    ga = _lib.larr(grid)
+    ptr = lambda t: C.c_void_p(t.data_ptr())                                          # noqa: E731
+    kinds = lambda *v: (C.c_int * 4)(*v)                                              # noqa: E731
+
+    def old(b):
+        out, lam = torch.zeros_like(U), torch.zeros(1, dtype=torch.float64, device="cuda")
+        _lib.check(lib.exa_fv_grid_step_device(k._plan, ptr(U), ptr(out), ga, b, None, 0.0, 1e-3, 0.1, ptr(lam), None))
+        return out.cpu().numpy(), float(lam[0])
+
+    def new(kd, b):
+        out, lam = torch.zeros_like(U), torch.zeros(1, dtype=torch.float64, device="cuda")
+        _lib.check(lib.exa_fv_grid_step_device_bc(k._plan, ptr(U), ptr(out), ga, kd, b, None, 0.0, 1e-3, 0.1, ptr(lam), None))
+        return out.cpu().numpy(), float(lam[0])
+    for a, b in ((old(None), new(kinds(0, 0, 0, 0), None)), (old(None), new(None, None)), (old(None), new(kinds(0, 0, 0, 0), ptr(bst))),
+                 (old(ptr(bst)), new(kinds(1, 1, 1, 1), ptr(bst)))):
+        assert np.array_equal(a[0], b[0]) and a[1] == b[1]
+    assert not np.array_equal(old(None)[0], old(ptr(bst))[0])
+    out = torch.zeros_like(U)
+    for kd, b, msg in ((kinds(0, 3, 0, 0), ptr(bst), "face_kind[1] = 3"), (kinds(0, 0, -1, 0), ptr(bst), "face_kind[2] = -1"),
+                       (kinds(0, 2, 0, 0), None, "needs face_data_dev"), (kinds(1, 0, 0, 0), None, "needs face_data_dev")):
+        assert lib.exa_fv_grid_step_device_bc(k._plan, ptr(U), ptr(out), ga, kd, b, None, 0.0, 1e-3, 0.1, None, None) != 0
+        assert msg in lib.exa_last_error().decode(), lib.exa_last_error().decode()
+    assert lib.exa_fv_grid_step_device_bc(k._plan, ptr(U), ptr(U), ga, None, None, None, 0.0, 1e-3, 0.1, None, None) != 0
+    assert "array of their own" in lib.exa_last_error().decode()
+    with pytest.raises(ValueError):
+        exa.FVPatchGrid(dim, grid, P, boundary={(0, 0): exa.Dirichlet(lambda x, t: x)})
+
+
+def test_example_walled_sod_tube(exa, capsys):
+    import importlib.util
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    spec = importlib.util.spec_from_file_location("sod_tube_fv_walls", os.path.join(root, "examples", "sod_tube_fv_walls.py"))
+    mod = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(mod)
+    gold = json.load(open(os.path.join(root, "tests", "golden", "fv_walls_sod.json")))
+    res = mod.main(gold["patches"], gold["patch_size"], gold["t_end"], gold["cfl"])
+    assert "L1(rho)" in capsys.readouterr().out
+    assert res["min_rho"] > 0 and res["min_p"] > 0
+    assert abs(res["l1"] - gold["l1_rho"]) <= 0.01 * gold["l1_rho"], (res, gold)
+    assert abs(res["steps"] - gold["steps"]) <= 1
