@@ -70,15 +70,18 @@ __device__ inline long fv_xcd_contiguous(long b, long n) {
     const long per = n / 8;
     return b < per * 8 ? (b % 8) * per + b / 8 : b;
 }
-// wave-level maximum -> one atomic per wave (non-negative doubles order like their bit patterns)
-__device__ inline void fv_lam_commit(double* lam, double mx) {
+// maximum over the lanes of a wave (every lane receives it)
+__device__ __forceinline__ double fv_wave_max(double mx) {
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) mx = nan_max(mx, __shfl_xor(mx, o, 64));
+    return mx;
+}
+// wave-level maximum -> one atomic per wave (non-negative doubles order like their bit patterns)
+__device__ inline void fv_lam_commit(double* lam, double mx) {
+    mx = fv_wave_max(mx);
     if ((threadIdx.x & 63) == 0) atomicMax(reinterpret_cast<unsigned long long*>(lam), (unsigned long long)__double_as_longlong(mx));
 }
 
-// grid step: where the stencil finds the state of volume `co` (coordinates with halo, exactly one of them in a halo layer: co[a] < H or >= P + H)
-// of patch `patch` -- the interior volume of the face neighbour it mirrors, or the boundary state of that domain face
 // grid coordinates of a patch (patch index row-major; 32-bit arithmetic: a 64-bit division costs ~100 instructions)
 template <int DIM>
 __device__ inline void fv_grid_coords(const FvCellData& cd, long patch, int* pg) {
@@ -87,13 +90,19 @@ __device__ inline void fv_grid_coords(const FvCellData& cd, long patch, int* pg)
     pg[1] = (int)(r % (unsigned)cd.g[1]);
     pg[0] = (int)(r / (unsigned)cd.g[1]);
 }
-// -> the kind of what lies there: FV_FACE_STATE: np = the face; FV_FACE_PERIODIC / FV_FACE_MIRROR: np, cn = patch and volume (coordinates with halo) whose
-// state it takes -- the face neighbour's, or (mirror) the patch's own, reflected at the face
+// interior coordinates (with halo) of volume id of a patch, volumes row-major
+template <int DIM>
+__device__ __forceinline__ void fv_volume_coords(int id, int P, int H, int* co) {
+    if constexpr (DIM == 3) { co[0] = id / (P * P) + H; co[1] = (id / P) % P + H; co[2] = id % P + H; }
+    else { co[0] = id / P + H; co[1] = id % P + H; co[2] = 0; }
+}
+// THE ghost rule of the grid step, patch part: what lies beyond face (a, side) of the patch at grid coordinates pgc (fbits: fv_face_bits).
+// -> its kind.  FV_FACE_STATE: np = the face, whose prescribed state it is; FV_FACE_PERIODIC / FV_FACE_MIRROR: np = row-major index of the patch whose
+// interior supplies the state -- the face neighbour (periodic wrap), or (mirror) the patch itself.
 // (MIR: the faces have kinds of their own, a mirror among them or not; the kernels are built with and without, and a launch whose faces are all
-// periodic or all prescribed states -- the only ones there were -- runs the code it always ran)
+// periodic or all prescribed states -- the only ones there were -- runs the code it always ran: no table of kinds is read)
 template <int DIM, bool MIR>
-__device__ inline int fv_grid_locate(const FvCellData& cd, const int* pgc, const int* co, int a, int P, int H, long& np, int* cn) {
-    const int side = co[a] < H ? 0 : 1;
+__device__ __forceinline__ int fv_face_neighbour(const FvCellData& cd, [[maybe_unused]] unsigned fbits, const int* pgc, int a, int side, long& np) {
     if constexpr (!MIR) {                                             // every domain face is periodic (no table) or a prescribed state
         int pg[3] = {pgc[0], pgc[1], pgc[2]};
         if (cd.bstate && (side == 0 ? pg[a] == 0 : pg[a] == cd.g[a] - 1)) { np = a * 2 + side; return FV_FACE_STATE; }
@@ -101,28 +110,36 @@ __device__ inline int fv_grid_locate(const FvCellData& cd, const int* pgc, const
         if (pg[a] < 0) pg[a] += cd.g[a];
         if (pg[a] >= cd.g[a]) pg[a] -= cd.g[a];
         np = DIM == 3 ? ((long)pg[0] * cd.g[1] + pg[1]) * cd.g[2] + pg[2] : (long)pg[0] * cd.g[1] + pg[1];
-#pragma unroll
-        for (int b = 0; b < DIM; b++) cn[b] = b == a ? (side == 0 ? co[b] + P : co[b] - P) : co[b];     // the interior volume it mirrors
         return FV_FACE_PERIODIC;
     }
-    const int kind = fv_face_kind(cd, fv_face_bits(cd), pgc[a], a, side);
-    if (kind == FV_FACE_STATE) { np = a * 2 + side; return kind; }    // domain face: the prescribed state
-    const bool own = kind == FV_FACE_MIRROR;
+    const int kind = fv_face_kind(cd, fbits, pgc[a], a, side);
+    if (kind == FV_FACE_STATE) { np = a * 2 + side; return kind; }
     int na = pgc[a];                                                  // (no private array indexed by a: selects)
-    if (!own) {
+    if (kind != FV_FACE_MIRROR) {
         na += side == 0 ? -1 : 1;
         if (na < 0) na += cd.g[a];
         if (na >= cd.g[a]) na -= cd.g[a];
     }
     const int p0 = a == 0 ? na : pgc[0], p1 = a == 1 ? na : pgc[1], p2 = a == 2 ? na : pgc[2];
     np = DIM == 3 ? ((long)p0 * cd.g[1] + p1) * cd.g[2] + p2 : (long)p0 * cd.g[1] + p1;
+    return kind;
+}
+// ... in-patch part: the coordinate (with halo) along the face's axis of the interior volume whose state the halo coordinate c takes -- the
+// neighbour's volume one patch further in, or (mirror) the patch's own at the same distance inside the face
+__device__ __forceinline__ int fv_ghost_coord(int kind, int side, int c, int P, int H) {
+    if (kind == FV_FACE_MIRROR) return (side == 0 ? 2 * H - 1 : 2 * (P + H) - 1) - c;
+    return side == 0 ? c + P : c - P;
+}
+// grid step: where the stencil finds the state of volume `co` (coordinates with halo, exactly one of them in a halo layer: co[a] < H or >= P + H)
+// of the patch at pgc -> the kind of what lies there, np as fv_face_neighbour gives it and (not for a prescribed state) cn = the volume in patch np
+template <int DIM, bool MIR>
+__device__ inline int fv_grid_locate(const FvCellData& cd, const int* pgc, const int* co, int a, int P, int H, long& np, int* cn) {
+    const int side = co[a] < H ? 0 : 1;
+    const int kind = fv_face_neighbour<DIM, MIR>(cd, MIR ? fv_face_bits(cd) : 0u, pgc, a, side, np);
+    if (kind == FV_FACE_STATE) return kind;
 #pragma unroll
-    for (int b = 0; b < DIM; b++) {
-        if (b != a) cn[b] = co[b];
-        else if (own) cn[b] = (side == 0 ? 2 * H - 1 : 2 * (P + H) - 1) - co[b];
-        else cn[b] = side == 0 ? co[b] + P : co[b] - P;                  // the interior volume it mirrors
-    }
-    return own ? FV_FACE_MIRROR : FV_FACE_PERIODIC;
+    for (int b = 0; b < DIM; b++) cn[b] = b == a ? fv_ghost_coord(kind, side, co[b], P, H) : co[b];
+    return kind;
 }
 // ... as an address in the halo-less array Q [patch][P^DIM][V].  sgn (optional): receives the V signs of a mirror face, null for the other kinds
 template <int DIM, bool MIR>
@@ -171,24 +188,8 @@ __device__ inline void fv_halo_volume(int e, int P, int H, int* co, int& a) {
 // SHAPE: compile-time (patch_size, halo_size, n_real, n_real + n_aux), or all zero for run-time values.  The reference's
 // own configuration (4, 1, 5, 10) is built specialised: the variable masks and the 64-bit index arithmetic fold away
 // (a wave executed ~1 030 VALU instructions in the generic build; the arithmetic and its order are the same).
-#ifndef EXA_FV_STORE
-#define EXA_FV_STORE 1
-#endif
-__device__ inline void fv_row_store(v2d val, v2d* at) {
-#if EXA_FV_STORE == 0
-    *at = val;
-#elif EXA_FV_STORE == 1
-    __builtin_nontemporal_store(val, at);
-#elif EXA_FV_STORE == 2
-    asm volatile("global_store_dwordx4 %0, %1, off sc0 sc1" ::"v"(at), "v"(val) : "memory");
-#elif EXA_FV_STORE == 3
-    asm volatile("global_store_dwordx4 %0, %1, off sc0 sc1 nt" ::"v"(at), "v"(val) : "memory");
-#elif EXA_FV_STORE == 4
-    asm volatile("global_store_dwordx4 %0, %1, off sc1" ::"v"(at), "v"(val) : "memory");
-#elif EXA_FV_STORE == 5
-    asm volatile("global_store_dwordx4 %0, %1, off sc0" ::"v"(at), "v"(val) : "memory");
-#endif
-}
+// streaming store of a row piece: the rows start at 80-byte offsets, i.e. partial cache lines -- do not allocate them in L2
+__device__ inline void fv_row_store(v2d val, v2d* at) { __builtin_nontemporal_store(val, at); }
 template <int TP, int TH, int TM, int TV> struct FvShape {
     static constexpr int P = TP, H = TH, M = TM, V = TV;
 };
@@ -199,11 +200,10 @@ using FvRuntimeShape = FvShape<0, 0, 0, 0>;
 // condition) before it updates the current one from LDS -- the 46 KB read of a block overlaps the stencil and the
 // write-back of its predecessor instead of standing alone in front of a barrier.
 constexpr int FV_HR = 16;          // double2 per thread that hold a block in flight (<= 64 KiB per block at 256 threads)
-#ifndef EXA_FV_GRID_WAVES
-#define EXA_FV_GRID_WAVES 1          // persistent grid step: no register cap (199 VGPRs, two workgroups per CU: 0.855 ms per 2^20-patch step); capped at 168 for
-#endif                               // three workgroups per CU it spills 31 registers and takes 0.995 ms
+// (persistent grid step: no register cap -- 199 VGPRs, two workgroups per CU: 0.855 ms per 2^20-patch step; capped at 168 for three workgroups per CU it
+// spills 31 registers and takes 0.995 ms)
 template <int DIM, class PDE, int MODE, int CPT, int NT, bool STAGE, class SHAPE = FvRuntimeShape, bool PERSIST = false, bool GRID = false, bool MIR = false>
-__global__ void __launch_bounds__(NT, ((GRID && PERSIST && NT == 256) ? EXA_FV_GRID_WAVES : 1))
+__global__ void __launch_bounds__(NT, 1)
 fv_rusanov_kernel(double* __restrict__ Q, int P_rt, int H_rt, int m_rt, int V_rt, double dt, double dt_over_h, long n_patches,
                   int ppb, const long* __restrict__ slot, FvCellData cd) {
     const int P = SHAPE::P ? SHAPE::P : P_rt, H = SHAPE::P ? SHAPE::H : H_rt;
@@ -236,11 +236,7 @@ fv_rusanov_kernel(double* __restrict__ Q, int P_rt, int H_rt, int m_rt, int V_rt
 #pragma unroll
         for (int r = 0; r < HRS; r++) {
             const int xx = (int)threadIdx.x + r * NT;
-#ifdef EXA_FV_NTLOAD
-            hold[r] = __builtin_nontemporal_load(s2 + (xx < npair ? xx : npair - 1));
-#else
             hold[r] = s2[xx < npair ? xx : npair - 1];
-#endif
         }
     };
     // grid step: the face-halo states of a block.  The patches of a block are consecutive along the LAST grid axis, so the halos beyond the
@@ -272,7 +268,6 @@ fv_rusanov_kernel(double* __restrict__ Q, int P_rt, int H_rt, int m_rt, int V_rt
     [[maybe_unused]] double hg[GWC * HG2];
     [[maybe_unused]] double lmax = 0.0;
     const int per = H * (DIM == 3 ? P * P : P);
-    const int nh = 2 * DIM * per;
     const int nA_pp = (DIM - 1) * 2 * per * V;                       // remote halo states per patch (faces of the axes 0 .. DIM - 2)
     // halo volume hv (numbering of fv_halo_volume: faces axis-major) of patch slot pp -> place in the LDS copy, source
     [[maybe_unused]] auto halo_place = [&](int pp, int hv, int (&co)[3], int& ax) -> int {
@@ -350,13 +345,14 @@ fv_rusanov_kernel(double* __restrict__ Q, int P_rt, int H_rt, int m_rt, int V_rt
             remote_elem(ppb, u * GWC, pp, hv, v);
             const int off = halo_place(pp, hv, co, ax);
             const int side = co[ax] < H ? 0 : 1;
+            // (the neighbour case of fv_ghost_coord, written out: through the function the staged run-time-shape kernels of the grid step take 7 to 15
+            // more VGPRs -- a wave per SIMD -- or spill: profiles/fv_unit_refactor.txt)
             int cg = 0;
 #pragma unroll
             for (int b = 0; b < DIM; b++) cg = cg * P + ((b == ax ? (side == 0 ? co[b] + P : co[b] - P) : co[b]) - H);
             // (mirror face: the patch's own volume at the same distance inside the face lies `dl` volumes along ax from the one a neighbour
             // would supply; kept in the bits above the face number)
-            const int layer = side == 0 ? co[ax] : co[ax] - P - H;
-            const int dl = side == 0 ? 2 * H - 1 - 2 * layer - P : P - 1 - 2 * layer;
+            const int dl = fv_ghost_coord(FV_FACE_MIRROR, side, co[ax], P, H) - fv_ghost_coord(FV_FACE_PERIODIC, side, co[ax], P, H);
             g_pp[r] = pp;
             g_face[r] = (mir ? dl * 8 : 0) + (ax * 2 + side);
             g_src[r] = cg * V + v;
@@ -364,30 +360,13 @@ fv_rusanov_kernel(double* __restrict__ Q, int P_rt, int H_rt, int m_rt, int V_rt
         }
     }
     [[maybe_unused]] auto unit_src = [&](int r, int half) -> const double* {
-        const int* pgc = pgtab + (half * ppb + g_pp[r]) * 3;
-        if constexpr (!mir) {
-            const int ax = g_face[r] >> 1, side = g_face[r] & 1;
-            int pg[3] = {pgc[0], pgc[1], pgc[2]};
-            if (cd.bstate && (side == 0 ? pg[ax] == 0 : pg[ax] == cd.g[ax] - 1)) return cd.bstate + (long)g_face[r] * V + (g_src[r] % V);
-            pg[ax] += side == 0 ? -1 : 1;
-            if (pg[ax] < 0) pg[ax] += cd.g[ax];
-            if (pg[ax] >= cd.g[ax]) pg[ax] -= cd.g[ax];
-            const long np = DIM == 3 ? ((long)pg[0] * cd.g[1] + pg[1]) * cd.g[2] + pg[2] : (long)pg[0] * cd.g[1] + pg[1];
-            return Q + np * ncell * V + g_src[r];
-        }
-        const int face = g_face[r] & 7, ax = face >> 1, side = face & 1;
-        const int kind = fv_face_kind(cd, fbits, pgc[ax], ax, side);
-        if (kind == FV_FACE_STATE) return cd.bstate + (long)face * V + (g_src[r] % V);
-        int na = pgc[ax], shift = 0;
+        const int face = mir ? g_face[r] & 7 : g_face[r], ax = face >> 1, side = face & 1;
+        long np;
+        const int kind = fv_face_neighbour<DIM, MIR>(cd, fbits, pgtab + (half * ppb + g_pp[r]) * 3, ax, side, np);
+        if (kind == FV_FACE_STATE) return cd.bstate + np * V + (g_src[r] % V);
+        int shift = 0;
         if (mir && kind == FV_FACE_MIRROR)                            // the patch itself, the reflected layer
             shift = (g_face[r] >> 3) * (DIM == 3 ? (ax == 0 ? P * P : (ax == 1 ? P : 1)) : (ax == 0 ? P : 1)) * V;
-        else {
-            na += side == 0 ? -1 : 1;
-            if (na < 0) na += cd.g[ax];
-            if (na >= cd.g[ax]) na -= cd.g[ax];
-        }
-        const int p0 = ax == 0 ? na : pgc[0], p1 = ax == 1 ? na : pgc[1], p2 = ax == 2 ? na : pgc[2];
-        const long np = DIM == 3 ? ((long)p0 * cd.g[1] + p1) * cd.g[2] + p2 : (long)p0 * cd.g[1] + p1;
         return Q + np * ncell * V + (g_src[r] + shift);
     };
     [[maybe_unused]] auto gather_request = [&](long blk, int half) {
@@ -523,12 +502,9 @@ fv_rusanov_kernel(double* __restrict__ Q, int P_rt, int H_rt, int m_rt, int V_rt
             // grid step: the face-halo volumes of the LDS copy take the neighbours' interior states (what a halo-fill pass would have
             // written into Q beforehand; here it costs no pass -- the lines are the ones the neighbours' own workgroups read)
             if constexpr (!PERSIST) __syncthreads();             // (the in-block copies read what the staging above wrote; PERSIST: barrier above)
-#ifndef EXA_FV_GRID_ABL          // (development: 1 = without the in-block copies, 2 = without the remote halos, 3 = neither -- timing only, wrong results)
-#define EXA_FV_GRID_ABL 0
-#endif
-            if constexpr ((EXA_FV_GRID_ABL & 1) == 0) gather_local(blk, PERSIST ? half : 0);
-            if constexpr ((EXA_FV_GRID_ABL & 2) == 0) gather_land(blk, PERSIST ? half : 0);
-            if constexpr (PERSIST && (EXA_FV_GRID_ABL & 2) == 0) {
+            gather_local(blk, PERSIST ? half : 0);
+            gather_land(blk, PERSIST ? half : 0);
+            if constexpr (PERSIST) {
                 if (blk + blk_step < nblk) gather_request(blk + blk_step, half ^ 1);
             }
         }
@@ -546,19 +522,8 @@ fv_rusanov_kernel(double* __restrict__ Q, int P_rt, int H_rt, int m_rt, int V_rt
         const int id = (CPT == 1) ? (int)threadIdx.x - pl * ncell : (int)threadIdx.x + k * NT;
         cidx[k] = -1;
         if (!live || id >= ncell) continue;
-#ifdef EXA_FV_ABL_NOCOMPUTE
-        {
-            int co[3];
-            if constexpr (DIM == 3) { co[0] = id / (P * P) + H; co[1] = (id / P) % P + H; co[2] = id % P + H; }
-            else { co[0] = id / P + H; co[1] = id % P + H; co[2] = 0; }
-            cidx[k] = co[0] * st[0] + co[1] * st[1] + co[2] * st[2];
-            for (int v = 0; v < MAXV; v++) nv[k][v] = v < m ? Qp[cidx[k] * V + v] : 0.0;
-            continue;
-        }
-#endif
         int co[3];
-        if constexpr (DIM == 3) { co[0] = id / (P * P) + H; co[1] = (id / P) % P + H; co[2] = id % P + H; }
-        else { co[0] = id / P + H; co[1] = id % P + H; co[2] = 0; }
+        fv_volume_coords<DIM>(id, P, H, co);
         // index of the volume where the stencil reads it: the layout with halo (HBM in place, or the LDS copy); a grid step without an LDS copy
         // reads the halo-less array, where a patch's volumes are numbered like the threads
         constexpr bool BARE = !STAGE && GRID;
@@ -748,9 +713,6 @@ fv_rusanov_kernel(double* __restrict__ Q, int P_rt, int H_rt, int m_rt, int V_rt
     }
     // every read of this patch is done (loads feed the values above) before any write
     __syncthreads();
-#ifdef EXA_FV_ABL_NOWRITE
-    if (rows) { if (nv[0][0] == 1.2345e-300) Q[0] = 0.0; rows = false; if constexpr (PERSIST) __syncthreads(); continue; }
-#endif
     if (rows) {
         double* Ql = fv_lds + (long)(live ? pl : 0) * vol * V;
 #pragma unroll
@@ -782,35 +744,14 @@ fv_rusanov_kernel(double* __restrict__ Q, int P_rt, int H_rt, int m_rt, int V_rt
         // (tried in r2: rows j in [H, P+H) with ALL k as one contiguous block per patch, the k-halo volumes rewriting their old
         // values -- no partial lines but +50 % bytes written at P = 4: 1.07 ms against 1.00 ms; the kernel moves its ACTUAL
         // 4.5 GB at 4.5 TB/s either way)
-#ifdef EXA_FV_WALIGN
-        // whole EXA_FV_WALIGN-byte units: a row's span is widened to the unit boundaries either side, the halo bytes in those units
-        // rewrite their own (unchanged) values from the LDS copy -- no partially written unit reaches the memory controller
-        constexpr int AL = EXA_FV_WALIGN / 8;
-        const int mis = (int)((reinterpret_cast<unsigned long long>(dst) >> 3) & (AL - 1));
-        const int slots = (P * V + 2 * (AL - 1) + 1) / 2;
-        for (long e = threadIdx.x; e < npatch * rows_pp * slots; e += NT) {
-            const long row = e / slots;
-            const int x = (int)(e - row * slots);
-            const long pp = row / rows_pp;
-            const int rr = (int)(row - pp * rows_pp);
-            const long o = pp * vol * V + ((DIM == 3) ? ((long)(rr / P + H) * S * S + (long)(rr % P + H) * S + H) : ((long)(rr + H) * S + H)) * V;
-            long lo = ((o + mis) & ~(long)(AL - 1)) - mis, hi = ((o + P * V + mis + AL - 1) & ~(long)(AL - 1)) - mis;
-            lo = lo < pp * vol * V ? pp * vol * V : lo;
-            hi = hi > (pp + 1) * vol * V ? (pp + 1) * vol * V : hi;
-            const long at = lo + 2 * x;
-            if (at < hi) __builtin_nontemporal_store(*reinterpret_cast<const v2d*>(fv_lds + at), reinterpret_cast<v2d*>(dst + at));
-        }
-#else
         for (long e = threadIdx.x; e < npatch * rows_pp * r2; e += NT) {
             const long row = e / r2;
             const int x = (int)(e - row * r2);
             const long pp = row / rows_pp;
             const int rr = (int)(row - pp * rows_pp);
             const long o = pp * vol * V + ((DIM == 3) ? ((long)(rr / P + H) * S * S + (long)(rr % P + H) * S + H) : ((long)(rr + H) * S + H)) * V;
-            // streaming store: the rows start at 80-byte offsets, i.e. partial cache lines -- do not allocate them in L2
             fv_row_store(reinterpret_cast<const v2d*>(fv_lds + o)[x], reinterpret_cast<v2d*>(dst + o) + x);
         }
-#endif
     } else {
 #pragma unroll
         for (int k = 0; k < CPT; k++) {
@@ -899,30 +840,26 @@ fv_rusanov_slab_kernel(double* __restrict__ Q, int P, int H, int m, int V, doubl
     // grid step: where plane i comes from -- this patch, or (i outside the interior planes) the neighbour along axis 0; a domain face of a
     // non-periodic grid has no plane: its ring slot is filled with the prescribed state (bnd_*) -- or, a mirror face (mir_*), takes the patch's own
     // plane at the same distance inside the face, every variable times its sign
-    [[maybe_unused]] const double* nb_lo = Qp;
+    [[maybe_unused]] const double* nb_lo = Qp;                     // the patches whose planes lie beyond the two faces of axis 0 (fv_face_neighbour)
     [[maybe_unused]] const double* nb_hi = Qp;
-    [[maybe_unused]] bool bnd_lo = false, bnd_hi = false, mir_lo = false, mir_hi = false;
+    [[maybe_unused]] int pgc[3] = {0, 0, 0}, klo = FV_FACE_PERIODIC, khi = FV_FACE_PERIODIC;
     [[maybe_unused]] const unsigned fbits = GRID ? fv_face_bits(cd) : 0u;
     constexpr bool mir = MIR;                                      // (the faces have kinds of their own: the dispatch launches this build for such a grid only)
     if constexpr (GRID) {
-        const long b = patch;
-        const int g0 = (int)(b / ((long)cd.g[1] * cd.g[2]));
-        const long rest = b - (long)g0 * cd.g[1] * cd.g[2];
-        const int klo = g0 == 0 ? (int)(fbits & 3u) : FV_FACE_PERIODIC, khi = g0 == cd.g[0] - 1 ? (int)((fbits >> 2) & 3u) : FV_FACE_PERIODIC;
-        bnd_lo = mir ? klo == FV_FACE_STATE : (cd.bstate && g0 == 0);
-        bnd_hi = mir ? khi == FV_FACE_STATE : (cd.bstate && g0 == cd.g[0] - 1);
-        mir_lo = mir && klo == FV_FACE_MIRROR;
-        mir_hi = mir && khi == FV_FACE_MIRROR;
-        const int gl = g0 == 0 ? cd.g[0] - 1 : g0 - 1, gh = g0 == cd.g[0] - 1 ? 0 : g0 + 1;
-        nb_lo = Q + ((long)gl * cd.g[1] * cd.g[2] + rest) * P * dplane;
-        nb_hi = Q + ((long)gh * cd.g[1] * cd.g[2] + rest) * P * dplane;
+        long np;
+        fv_grid_coords<3>(cd, patch, pgc);
+        klo = fv_face_neighbour<3, MIR>(cd, fbits, pgc, 0, 0, np);
+        if (klo != FV_FACE_STATE) nb_lo = Q + np * P * dplane;
+        khi = fv_face_neighbour<3, MIR>(cd, fbits, pgc, 0, 1, np);
+        if (khi != FV_FACE_STATE) nb_hi = Q + np * P * dplane;
     }
-    // plane i (index WITH halo) in HBM; grid step: halo-less planes, the ones beyond the patch from the neighbours' interiors (a boundary
+    [[maybe_unused]] const bool bnd_lo = klo == FV_FACE_STATE, bnd_hi = khi == FV_FACE_STATE, mir_lo = mir && klo == FV_FACE_MIRROR, mir_hi = mir && khi == FV_FACE_MIRROR;
+    // plane i (index WITH halo) in HBM; grid step: halo-less planes, the ones beyond the patch from the interior the ghost rule names (a boundary
     // plane has no source: any valid address, its ring slot is filled with the state)
     auto plane_src = [&](int i) -> const double* {
         if constexpr (GRID) {
-            if (i < H) return mir_lo ? Qp + (long)(H - 1 - i) * dplane : (bnd_lo ? Qp : nb_lo + (long)(i + P - H) * dplane);
-            if (i >= P + H) return mir_hi ? Qp + (long)(2 * P + H - 1 - i) * dplane : (bnd_hi ? Qp : nb_hi + (long)(i - P - H) * dplane);
+            if (i < H) return bnd_lo ? Qp : nb_lo + (long)(fv_ghost_coord(mir_lo ? FV_FACE_MIRROR : FV_FACE_PERIODIC, 0, i, P, H) - H) * dplane;
+            if (i >= P + H) return bnd_hi ? Qp : nb_hi + (long)(fv_ghost_coord(mir_hi ? FV_FACE_MIRROR : FV_FACE_PERIODIC, 1, i, P, H) - H) * dplane;
             return Qp + (long)(i - H) * dplane;
         }
         return Qp + (long)i * plane;
@@ -1011,8 +948,6 @@ fv_rusanov_slab_kernel(double* __restrict__ Q, int P, int H, int m, int V, doubl
     [[maybe_unused]] int hsgn[GRID ? SLAB_NH : 1];                 // entry of cd.bstate that holds the value's sign (a mirror face), or -1
     if constexpr (GRID) {
         const int nhe = 4 * H * P * V;
-        int pgc[3];
-        fv_grid_coords<3>(cd, patch, pgc);
 #pragma unroll
         for (int r = 0; r < SLAB_NH; r++) {
             const int e0 = tid + r * SLAB_NT, e = e0 < nhe ? e0 : nhe - 1;
@@ -1333,8 +1268,7 @@ __global__ void fv_maxeig_kernel(const double* __restrict__ Q, int P, int H, int
         const long patch = i / ncell;
         const int id = (int)(i - patch * ncell);
         int co[3];
-        if constexpr (DIM == 3) { co[0] = id / (P * P) + H; co[1] = (id / P) % P + H; co[2] = id % P + H; }
-        else { co[0] = id / P + H; co[1] = id % P + H; co[2] = 0; }
+        fv_volume_coords<DIM>(id, P, H, co);
         const long c = DIM == 3 ? ((long)co[0] * S + co[1]) * S + co[2] : (long)co[0] * S + co[1];
         const double* qp = Q + (patch * vol + c) * V;
         double q[MAXV];
@@ -1348,8 +1282,7 @@ __global__ void fv_maxeig_kernel(const double* __restrict__ Q, int P, int H, int
 #pragma unroll
         for (int d = 0; d < DIM; d++) mx = nan_max(mx, fv_eig<PDE>(q, x, t, d));
     }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) mx = nan_max(mx, __shfl_xor(mx, o, 64));
+    mx = fv_wave_max(mx);
     __shared__ double wm[4];
     if ((threadIdx.x & 63) == 0) wm[threadIdx.x >> 6] = mx;
     __syncthreads();
@@ -1399,6 +1332,9 @@ static int fv_dispatch(int P, int H, int m, int V, long n_patches, double* Q, do
     const double doh = (MODE == 1) ? dt / h : 0.0;
     const int S = P + 2 * H;
     const long pvol = (DIM == 3) ? (long)S * S * S : (long)S * S;
+    auto launch = [&](auto kern, dim3 grid, unsigned nt, size_t lds, int ppb) {
+        hipLaunchKernelGGL(kern, grid, dim3(nt), lds, s, Q, P, H, m, V, dt, doh, n_patches, ppb, slot, cd);
+    };
     if (ncell <= 256) {
         const int ppb = (int)(256 / ncell);
         const dim3 grid((unsigned)((n_patches + ppb - 1) / ppb));
@@ -1416,42 +1352,21 @@ static int fv_dispatch(int P, int H, int m, int V, long n_patches, double* Q, do
             return (unsigned)(g < nb ? g : nb);
         };
         if (DIM == 2 && P == 4 && H == 1 && m == 5 && V == 10) {    // the reference's configuration (Batched_stateless.py:9)
-#ifdef EXA_FV_REF_NT
-            {
-                constexpr int RNT = EXA_FV_REF_NT;
-                const int rppb = RNT / 16;
-                const size_t rlds = (size_t)rppb * pvol * V * sizeof(double) + (GRID ? (size_t)rppb * 32 : 0);
-                auto kr = fv_rusanov_kernel<DIM, PDE, MODE, 1, RNT, true, FvShape<4, 1, 5, 10>, true, GRID, MIR>;
-                int per_cu = 0, dev = 0, cus = 0;
-                hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, reinterpret_cast<const void*>(kr), RNT, rlds);
-                hipGetDevice(&dev);
-                hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
-                const long g = (long)per_cu * cus, nb = (n_patches + rppb - 1) / rppb;
-                if (persist && g > 0 && n_patches >= (long)rppb * 8192) {
-                    static bool said = false;
-                    if (!said) { fprintf(stderr, "fv ref: NT %d ppb %d per_cu %d\n", RNT, rppb, per_cu); said = true; }
-                    hipLaunchKernelGGL(kr, dim3((unsigned)(g < nb ? g : nb)), dim3(RNT), rlds, s, Q, P, H, m, V, dt, doh, n_patches, rppb, slot, cd);
-                    hipError_t e = hipGetLastError();
-                    if (e != hipSuccess) { set_error("fv_rusanov launch: %s", hipGetErrorString(e)); return -2; }
-                    return 0;
-                }
-            }
-#endif
             auto kp = fv_rusanov_kernel<DIM, PDE, MODE, 1, 256, true, FvShape<4, 1, 5, 10>, true, GRID, MIR>;
             const unsigned pg = persist ? persist_grid(reinterpret_cast<const void*>(kp)) : 0;
-            if (pg > 0) hipLaunchKernelGGL(kp, dim3(pg), dim3(256), lds, s, Q, P, H, m, V, dt, doh, n_patches, ppb, slot, cd);
-            else hipLaunchKernelGGL((fv_rusanov_kernel<DIM, PDE, MODE, 1, 256, true, FvShape<4, 1, 5, 10>, false, GRID, MIR>), grid, dim3(256), lds, s, Q, P, H, m, V, dt, doh, n_patches, ppb, slot, cd);
+            if (pg > 0) launch(kp, dim3(pg), 256, lds, ppb);
+            else launch(fv_rusanov_kernel<DIM, PDE, MODE, 1, 256, true, FvShape<4, 1, 5, 10>, false, GRID, MIR>, grid, 256, lds, ppb);
         } else if (lds <= 64 * 1024)     // staged: several workgroups per CU keep HBM requests in flight (the persistent form
                                          // with its 64 holding VGPRs lost there: 2-D P = 16 0.55 -> 0.67 ms)
-            hipLaunchKernelGGL((fv_rusanov_kernel<DIM, PDE, MODE, 1, 256, true, FvRuntimeShape, false, GRID, MIR>), grid, dim3(256), lds, s, Q, P, H, m, V, dt, doh, n_patches, ppb, slot, cd);
+            launch(fv_rusanov_kernel<DIM, PDE, MODE, 1, 256, true, FvRuntimeShape, false, GRID, MIR>, grid, 256, lds, ppb);
         else
-            hipLaunchKernelGGL((fv_rusanov_kernel<DIM, PDE, MODE, 1, 256, false, FvRuntimeShape, false, GRID, MIR>), grid, dim3(256), 0, s, Q, P, H, m, V, dt, doh, n_patches, ppb, slot, cd);
+            launch(fv_rusanov_kernel<DIM, PDE, MODE, 1, 256, false, FvRuntimeShape, false, GRID, MIR>, grid, 256, 0, ppb);
     } else if (ncell <= 1024) {
         const size_t lds = (size_t)pvol * V * sizeof(double) + (GRID ? 32 : 0);
         if (lds <= 64 * 1024)
-            hipLaunchKernelGGL((fv_rusanov_kernel<DIM, PDE, MODE, 1, 1024, true, FvRuntimeShape, false, GRID, MIR>), dim3((unsigned)n_patches), dim3(1024), lds, s, Q, P, H, m, V, dt, doh, n_patches, 1, slot, cd);
+            launch(fv_rusanov_kernel<DIM, PDE, MODE, 1, 1024, true, FvRuntimeShape, false, GRID, MIR>, dim3((unsigned)n_patches), 1024, lds, 1);
         else
-            hipLaunchKernelGGL((fv_rusanov_kernel<DIM, PDE, MODE, 1, 1024, false, FvRuntimeShape, false, GRID, MIR>), dim3((unsigned)n_patches), dim3(1024), 0, s, Q, P, H, m, V, dt, doh, n_patches, 1, slot, cd);
+            launch(fv_rusanov_kernel<DIM, PDE, MODE, 1, 1024, false, FvRuntimeShape, false, GRID, MIR>, dim3((unsigned)n_patches), 1024, 0, 1);
     } else if (DIM == 3 && P * P <= 256 && S * S * V <= 2 * SLAB_NR * SLAB_NT && !pde_has_xt<PDE>::value && !pde_has_ncp<PDE>::value &&
                (!cd.out || GRID) && (!GRID || 4 * H * P * V <= SLAB_NH * SLAB_NT)) {
         // plane-streaming variant: 3-plane LDS ring (+ 2 planes of per-volume scalars), one workgroup per patch
@@ -1466,7 +1381,7 @@ static int fv_dispatch(int P, int H, int m, int V, long n_patches, double* Q, do
         }
         hipLaunchKernelGGL(kern, dim3((unsigned)n_patches), dim3(SLAB_NT), lds, s, Q, P, H, m, V, dt, doh, slot, cd);
     } else if (ncell <= 4096) {
-        hipLaunchKernelGGL((fv_rusanov_kernel<DIM, PDE, MODE, 4, 1024, false, FvRuntimeShape, false, GRID, MIR>), dim3((unsigned)n_patches), dim3(1024), 0, s, Q, P, H, m, V, dt, doh, n_patches, 1, slot, cd);
+        launch(fv_rusanov_kernel<DIM, PDE, MODE, 4, 1024, false, FvRuntimeShape, false, GRID, MIR>, dim3((unsigned)n_patches), 1024, 0, 1);
     }
     else {
         set_error("FV patch with %ld volumes exceeds the 4096 a workgroup keeps in registers", ncell);
@@ -1484,6 +1399,12 @@ static int fv_mode(int mode, int P, int H, int m, int V, long n_patches, double*
     // mirror's code (MIR); every other launch the ones without
     bool mirror = false;
     for (int f = 0; f < 2 * DIM; f++) mirror = mirror || (cd.bstate && cd.bkind[f] != FV_FACE_STATE);
+    auto go = [&](auto mode_c) {
+        constexpr int MODE = decltype(mode_c)::value;
+        if (cd.grid_on && mirror) return fv_dispatch<DIM, PDE, MODE, true, true>(P, H, m, V, n_patches, Q, dt, h, slot, s, cd);
+        if (cd.grid_on) return fv_dispatch<DIM, PDE, MODE, true>(P, H, m, V, n_patches, Q, dt, h, slot, s, cd);
+        return fv_dispatch<DIM, PDE, MODE, false>(P, H, m, V, n_patches, Q, dt, h, slot, s, cd);
+    };
     if (mode == 0) {
         // the faithful mode IS the reference's statement list (test.cpp:60-95): it has no source and no non-conservative product -- a term
         // set that carries one would be integrated as a different PDE without a word
@@ -1491,17 +1412,20 @@ static int fv_mode(int mode, int P, int H, int m, int V, long n_patches, double*
             set_error("FV faithful mode (the reference's statement list) has no source / ncp term: use EXA_FV_RUSANOV for this term set");
             return -1;
         } else {
-            if (cd.grid_on && mirror) return fv_dispatch<DIM, PDE, 0, true, true>(P, H, m, V, n_patches, Q, dt, h, slot, s, cd);
-            if (cd.grid_on) return fv_dispatch<DIM, PDE, 0, true>(P, H, m, V, n_patches, Q, dt, h, slot, s, cd);
-            return fv_dispatch<DIM, PDE, 0, false>(P, H, m, V, n_patches, Q, dt, h, slot, s, cd);
+            return go(std::integral_constant<int, 0>{});
         }
     }
     if constexpr (pde_has_xt<PDE>::value) {
         if (slot && !cd.centre) { set_error("FV Rusanov: the masked patch update of a term set whose terms depend on position / time needs the patch centres (exa_fv_time_step_device_masked_at)"); return -1; }
     }
-    if (cd.grid_on && mirror) return fv_dispatch<DIM, PDE, 1, true, true>(P, H, m, V, n_patches, Q, dt, h, slot, s, cd);
-    if (cd.grid_on) return fv_dispatch<DIM, PDE, 1, true>(P, H, m, V, n_patches, Q, dt, h, slot, s, cd);
-    return fv_dispatch<DIM, PDE, 1, false>(P, H, m, V, n_patches, Q, dt, h, slot, s, cd);
+    return go(std::integral_constant<int, 1>{});
+}
+
+// the launch's arguments as the kernels take them
+static FvCellData make_cd(double* out, const double* centre, double t, double h, const FvGridArgs* grid) {
+    FvCellData cd{out, centre, t, h, nullptr, {1, 1, 1}, nullptr, 0, {0, 0, 0, 0, 0, 0}};
+    if (grid) { cd.out = grid->out; cd.bstate = grid->bstate; cd.lam = grid->lam; cd.grid_on = 1; for (int a = 0; a < 3; a++) cd.g[a] = grid->g[a]; for (int f = 0; f < 6; f++) cd.bkind[f] = grid->bkind[f]; }
+    return cd;
 }
 
 #ifdef EXA_USER_PDE_HEADER
@@ -1511,11 +1435,6 @@ extern "C" int exa_user_nv() { return exa::UserPDE::NV; }
 // bit 0: the terms depend on position / time (HAS_XT), bit 1: the term set carries a non-conservative product (HAS_NCP)
 extern "C" int exa_user_pde_flags() {
     return (exa::pde_has_xt<exa::UserPDE>::value ? 1 : 0) | (exa::pde_has_ncp<exa::UserPDE>::value ? 2 : 0) | (exa::pde_has_admissible<exa::UserPDE>::value ? 4 : 0);
-}
-static exa::FvCellData make_cd(double* out, const double* centre, double t, double h, const exa::FvGridArgs* grid) {
-    exa::FvCellData cd{out, centre, t, h, nullptr, {1, 1, 1}, nullptr, 0, {0, 0, 0, 0, 0, 0}};
-    if (grid) { cd.out = grid->out; cd.bstate = grid->bstate; cd.lam = grid->lam; cd.grid_on = 1; for (int a = 0; a < 3; a++) cd.g[a] = grid->g[a]; for (int f = 0; f < 6; f++) cd.bkind[f] = grid->bkind[f]; }
-    return cd;
 }
 extern "C" int exa_user_fv_maxeig(int dim, int P, int H, int n_real, int n_aux, long n_patches, const double* Q, double* lam, void* stream,
                                   const double* centre, double t, double h) {
@@ -1566,8 +1485,7 @@ int fv_maxeig_launch(int dim, int P, int H, int n_real, int n_aux, long n_patche
 int fv_launch(int mode, int dim, int P, int H, int n_real, int n_aux, long n_patches, int pde, double* Q, double dt,
               double h, const long* slot, hipStream_t s, double* out, const double* centre, double t, const FvGridArgs* grid) {
     const int V = n_real + n_aux;
-    FvCellData cd{out, centre, t, h, nullptr, {1, 1, 1}, nullptr, 0, {0, 0, 0, 0, 0, 0}};
-    if (grid) { cd.out = grid->out; cd.bstate = grid->bstate; cd.lam = grid->lam; cd.grid_on = 1; for (int a = 0; a < 3; a++) cd.g[a] = grid->g[a]; for (int f = 0; f < 6; f++) cd.bkind[f] = grid->bkind[f]; }
+    const FvCellData cd = make_cd(out, centre, t, h, grid);
     if (grid && grid->lam) {
         hipError_t e0 = hipMemsetAsync(grid->lam, 0, sizeof(double), s);
         if (e0 != hipSuccess) { set_error("memset: %s", hipGetErrorString(e0)); return -2; }

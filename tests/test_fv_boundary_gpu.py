@@ -9,7 +9,9 @@
     outflow); layout (i) sets two mirrors with different signs against each other (wall | outflow), layout (iii) two equal ones.
 (b) the fused step is bit-equal to the two-pass form (torch halo fill, in-place update) on the same shapes; with_halo() of the fused grid holds, in
     the halo layer next to every patch face, what the restatement pads the global array of the device's states with (tests/fv_boundary_ref.py
-    padded: a path that shares no code with the torch fill), and is the two-pass array elsewhere on the stencil's halo entries.
+    padded: a path that shares no code with the torch fill), and is the two-pass array elsewhere on the stencil's halo entries.  The persistent
+    form of the reference's configuration (decoded remote halos, coordinate table in two halves) needs 2048 blocks of 16 patches: one grid of
+    65 x 505 patches, blocks that straddle the rows, a ragged last block; interior and fused CFL scalar only.
 (c) a wall is a mirror: the walled run is bit-equal to the left half of a periodic run on the mirrored domain.
 (d) a closed box conserves mass and energy to rounding; a constant state under outflow is a fixed point.
 (e) a generated term set (shallow water) through its side library.
@@ -50,7 +52,9 @@ SHAPES = [
     ("staged", 3, 6, 2, 3, (1, 2, 1), E),
 ]
 LAYOUTS = ("wall-outflow-x", "every-face", "all-walls")
-FAMILY = {"wall-outflow-x": "benign", "every-face": "supersonic", "all-walls": "riemann"}
+FAMILY = {"wall-outflow-x": "benign", "every-face": "supersonic", "all-walls": "riemann", "all-states": "supersonic"}
+# 32 825 patches = 2 051 full blocks of 16 + one of 9; 505 is no multiple of 16: a periodic wrap would fall inside a block
+PERSISTENT = ("ref-persistent", 2, 4, 1, 5, (65, 505), E)
 
 
 def _row(shape):
@@ -62,7 +66,7 @@ def _id(shape):
     return K.row_id(_row(shape)).replace("grid_periodic_", "")
 
 
-for _s in SHAPES:
+for _s in SHAPES + [PERSISTENT]:
     assert K.branch(*_row(_s)[1:]) == _s[0], _s
 
 
@@ -88,6 +92,8 @@ def _boundary(exa, shape, layout):
         return {(0, 0): exa.Wall() if euler else exa.Dirichlet(st[0]), (0, 1): exa.Outflow()}
     if layout == "all-walls":
         return {(a, s): exa.Wall() if euler else exa.Outflow() for a in range(dim) for s in range(2)}
+    if layout == "all-states":                                  # a prescribed state on every face: the kernels built without the per-face kinds
+        return {(a, s): st[a * 2 + s] for a in range(dim) for s in range(2)}
     wall = (lambda a: exa.Wall()) if euler else (lambda a: exa.Outflow())
     faces = {(0, 0): wall(0), (0, 1): exa.Dirichlet(st[1]), (1, 0): st[2], (1, 1): exa.Outflow()}
     if dim == 3:
@@ -164,6 +170,22 @@ def test_fused_step_is_the_two_pass_form(exa, shape, layout):
                 assert np.array_equal(cut[idx][tuple(sel)], pad[tuple(glob)]), (idx, ax, side)
     assert np.array_equal(a[(slice(None),) * dim + (out == 1,)], b[(slice(None),) * dim + (out == 1,)])
     assert np.array_equal(a[(slice(None),) * dim + (out == 0,)], b[(slice(None),) * dim + (out == 0,)])
+
+
+@pytest.mark.parametrize("layout", ("every-face", "all-states"))
+def test_persistent_fused_step_is_the_two_pass_form(exa, layout):
+    """the persistent grid kernel with domain faces that are not periodic: three steps, interior bit-equal to the two-pass form, the fused CFL
+    scalar bit-equal to the scan of that same interior (the two-pass form's pieces are held to the long-double bound elsewhere)"""
+    g, dt, kinds, data = _grid(exa, PERSISTENT, layout)
+    two, _, _, _ = _grid(exa, PERSISTENT, layout, fused=False)
+    assert (B.MIRROR in kinds) == (layout == "every-face") and B.STATE in kinds
+    for step in range(3):
+        g.step(dt)
+        two.step(dt)
+        assert np.array_equal(g.interior(), two.interior()), (step, layout)
+        fused = g.max_eigenvalue()
+        g.invalidate()
+        assert fused == g.max_eigenvalue(), (step, layout)
 
 
 def _mirrored(U, dim):
