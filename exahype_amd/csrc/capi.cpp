@@ -48,6 +48,10 @@ struct UserPde {
     int k_dmp;
     int (*lim_snap)(int, int, long, const double*, double*, double*, void*);
     int (*lim_det)(int, int, const long*, const double*, const double*, const double* const*, const int*, double, double, double, unsigned char*, void*);
+    // the term set's instantiation of the limiter's conservative interface (EXA_PDE_FLAG_CONSERVATIVE; lim_conserve_user.hip)
+    int (*lim_flux)(int, int, const double*, const long*, long, double*, const double*, void*);
+    int (*lim_corr)(int, int, const long*, double*, const double*, const long*, long, const unsigned char*, const int*, const double*, double, const double*,
+                    const double*, const double*, const double*, void*);
 };
 static std::vector<UserPde> g_user;
 
@@ -153,6 +157,15 @@ int exa_register_pde(const char* library_path, int* pde_id) {
             return EXA_ERR_INVALID;
         }
         u.k_dmp = kf();
+    }
+    if (u.flags & EXA_PDE_FLAG_CONSERVATIVE) {
+        u.lim_flux = (decltype(u.lim_flux))dlsym(h, "exa_user_lim_face_flux");
+        u.lim_corr = (decltype(u.lim_corr))dlsym(h, "exa_user_lim_interface_correct");
+        if (!u.lim_flux || !u.lim_corr) {
+            dlclose(h);
+            set_error("%s asks for the conservative DG / FV interface but exports no exa_user_lim_face_flux / exa_user_lim_interface_correct", library_path);
+            return EXA_ERR_INVALID;
+        }
     }
     g_user.push_back(u);
     *pde_id = 100 + (int)g_user.size() - 1;
@@ -746,15 +759,24 @@ int exa_lim_detect(exa_dg_plan* p, const double* u_cand_dev, const double* bound
     return limiter_detect(p->dim, p->N, p->nv, p->nc, u_cand_dev, bounds_dev, &gb, face_kind, d0, eps, floor, mask_dev, (hipStream_t)stream);
 }
 
-// term sets the conservative interface is built for: the built-in Euler (5 variables) and advection (1 variable) sets
-static int lim_conservative_pde(const exa_dg_plan* p, const char* who) {
+// term sets the conservative interface is built for: the built-in Euler (5 variables) and advection (1 variable) sets, and registered sets that
+// ask for it (EXA_PDE_FLAG_CONSERVATIVE) -- *user then points to the registered one
+static int lim_conservative_pde(const exa_dg_plan* p, const char* who, const UserPde** user) {
+    *user = nullptr;
     if (exa_pde_flags(p->pde) & (EXA_PDE_FLAG_XT | EXA_PDE_FLAG_NCP)) {
-        set_error("%s: term set %d carries position- / time-dependent terms or a non-conservative product; the conservative interface is built for the built-in Euler and advection sets", who, p->pde);
+        set_error("%s: term set %d carries position- / time-dependent terms or a non-conservative product; the conservative interface is built for "
+                  "term sets of the state alone without one", who, p->pde);
         return EXA_ERR_INVALID;
     }
+    if (exa_pde_flags(p->pde) & EXA_PDE_FLAG_CONSERVATIVE) {
+        const UserPde* u = &g_user[p->pde - 100];
+        if (p->nv != u->nv) { set_error("%s: term set %d has %d variables, the plan %d", who, p->pde, u->nv, p->nv); return EXA_ERR_INVALID; }
+        *user = u;
+        return EXA_OK;
+    }
     if (!((p->pde == 1 && p->nv == 5) || (p->pde == 2 && p->nv == 1))) {
-        set_error("%s: term set %d with %d variables; the conservative interface is built for the built-in Euler (pde 1, 5 variables) and advection (pde 2, 1 variable) sets, "
-                  "not for registered ones", who, p->pde, p->nv);
+        set_error("%s: term set %d with %d variables; the conservative interface is built for the built-in Euler (pde 1, 5 variables) and advection (pde 2, 1 variable) sets "
+                  "and for registered sets generated with SympyPDE(conservative_interface=True)", who, p->pde, p->nv);
         return EXA_ERR_INVALID;
     }
     return EXA_OK;
@@ -766,13 +788,14 @@ int exa_lim_face_flux(exa_dg_plan* p, const double* patch_dev, const long* cells
     if (!p || n < 0 || (n > 0 && (!patch_dev || !cells_dev || !fvflux_dev))) { set_error("exa_lim_face_flux: bad argument (NULL plan or array, or n < 0)"); return EXA_ERR_INVALID; }
     int rc = use_device(p->device);
     if (rc) return rc;
-    rc = lim_conservative_pde(p, "exa_lim_face_flux");
+    const UserPde* up;
+    rc = lim_conservative_pde(p, "exa_lim_face_flux", &up);
     if (rc) return rc;
     rc = lim_tables(p);
     if (rc) return rc;
-    const int Ns = 2 * p->N - 1;
-    return limiter_face_flux(p->dim, p->N, p->pde, patch_dev, cells_dev, n, fvflux_dev, static_cast<const double*>(p->ops.lim) + (size_t)p->N * Ns,
-                             (hipStream_t)stream) == 0 ? EXA_OK : EXA_ERR_HIP;
+    const double* Rdev = static_cast<const double*>(p->ops.lim) + (size_t)p->N * (2 * p->N - 1);
+    if (up) return up->lim_flux(p->dim, p->N, patch_dev, cells_dev, n, fvflux_dev, Rdev, stream) == 0 ? EXA_OK : EXA_ERR_HIP;
+    return limiter_face_flux(p->dim, p->N, p->pde, patch_dev, cells_dev, n, fvflux_dev, Rdev, (hipStream_t)stream) == 0 ? EXA_OK : EXA_ERR_HIP;
 }
 
 int exa_lim_interface_correct(exa_dg_plan* p, double* u_dev, const double* trace_dev, const long* cells_dev, long n, const unsigned char* mask_dev,
@@ -783,7 +806,8 @@ int exa_lim_interface_correct(exa_dg_plan* p, double* u_dev, const double* trace
     }
     int rc = use_device(p->device);
     if (rc) return rc;
-    rc = lim_conservative_pde(p, "exa_lim_interface_correct");
+    const UserPde* up;
+    rc = lim_conservative_pde(p, "exa_lim_interface_correct", &up);
     if (rc) return rc;
     for (int f = 0; f < 2 * p->dim; f++) {
         const int kind = face_kind ? face_kind[f] : EXA_LIM_FACE_PERIODIC;
@@ -795,6 +819,9 @@ int exa_lim_interface_correct(exa_dg_plan* p, double* u_dev, const double* trace
     }
     for (int a = 0; a < p->dim; a++)
         if (!(dx[a] > 0.0)) { set_error("exa_lim_interface_correct: dx[%d] must be positive", a); return EXA_ERR_INVALID; }
+    if (up)
+        return up->lim_corr(p->dim, p->N, p->nc, u_dev, trace_dev, cells_dev, n, mask_dev, face_kind, fvflux_dev, dt, dx, p->ops.w, p->ops.phiL, p->ops.phiR,
+                            stream) == 0 ? EXA_OK : EXA_ERR_HIP;
     return limiter_interface_correct(p->dim, p->N, p->pde, p->nc, u_dev, trace_dev, cells_dev, n, mask_dev, face_kind, fvflux_dev, dt, dx,
                                      p->ops.w, p->ops.phiL, p->ops.phiR, (hipStream_t)stream) == 0 ? EXA_OK : EXA_ERR_HIP;
 }

@@ -80,6 +80,12 @@ template <class PDE> __device__ inline void fv_ncp(const double* q, const double
 // without it is checked in the Euler layout (density first, energy last).  pde_codegen.SympyPDE(admissible=..., dmp=...) generates one.
 template <class P, class = void> struct pde_has_admissible : std::false_type {};
 template <class P> struct pde_has_admissible<P, std::void_t<decltype(P::HAS_ADMISSIBLE)>> : std::bool_constant<P::HAS_ADMISSIBLE> {};
+// Optional: `static constexpr bool HAS_CONSERVATIVE_INTERFACE = true` -- the term set asks for the conservative DG / FV interface of the
+// a-posteriori subcell limiter (exa_lim_conserve.hpp): its side library then carries its own instantiation of the two kernels
+// (lim_conserve_user.hip).  Only for term sets of the state alone without a non-conservative product: the face flux is
+// flux_rt / maxeig.  pde_codegen.SympyPDE(conservative_interface=True) generates the marker.
+template <class P, class = void> struct pde_has_conservative_interface : std::false_type {};
+template <class P> struct pde_has_conservative_interface<P, std::void_t<decltype(P::HAS_CONSERVATIVE_INTERFACE)>> : std::bool_constant<P::HAS_CONSERVATIVE_INTERFACE> {};
 
 // The same terms for the ADER-DG kernels (tolerance 1e-10): generated term sets carry `_fast` twins whose reciprocals / square roots use the
 // fast sequences below (pde_codegen.py); a term set without them is evaluated as it is.

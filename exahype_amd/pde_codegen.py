@@ -117,7 +117,8 @@ def _arity(fn):
 
 
 class SympyPDE:
-    def __init__(self, n_vars, flux, max_eigenvalue, max_dim=3, name="user", source=None, ncp=None, max_aux=None, admissible=None, dmp=None):
+    def __init__(self, n_vars, flux, max_eigenvalue, max_dim=3, name="user", source=None, ncp=None, max_aux=None, admissible=None, dmp=None, *,
+                 conservative_interface=False):
         """flux(q, d) -> n_vars expressions, max_eigenvalue(q, d) -> one, in the state symbols q; d = 0-based normal.
         source(q) -> n_vars expressions (optional): the algebraic source S(q) of q_t + div F(q) = S(q) -- the hook the
         reference's harness declares beside flux and maxEigenvalue (`Unit test/correctness_test.cpp:16-23`).  It enters the
@@ -142,7 +143,13 @@ class SympyPDE:
         (() = positivity and finiteness only).  `dmp` alone is allowed (no expression, K_ADM = 0); `admissible` alone watches nothing.  With
         either, the generated struct carries HAS_ADMISSIBLE and the side library its own instantiation of the detection kernels
         (csrc/lim_user.hip); without both, the detector assumes the Euler layout (density first, energy last) and the generated source is
-        what it was."""
+        what it was.
+
+        conservative_interface=True (keyword only): the term set asks for the conservative DG / FV interface of the a-posteriori limiter
+        (SubcellLimiter.step / step_a_posteriori / run with conservative=True).  The generated struct then carries HAS_CONSERVATIVE_INTERFACE and
+        the side library its own instantiation of the two interface kernels (csrc/lim_conserve_user.hip): the FV face flux is the Rusanov
+        flux of flux / max_eigenvalue, which a source term does not enter.  Not for terms that depend on position / time and not together
+        with an ncp (ValueError); without the keyword the generated source is what it was."""
         if not 1 <= n_vars <= 8:
             raise ValueError("n_vars must be 1..8")
         self.n_vars, self.max_dim, self.name = n_vars, max_dim, name
@@ -196,6 +203,13 @@ class SympyPDE:
                 raise ValueError("dmp: variable indices must be in 0..%d, got %s" % (n_vars - 1, self.dmp_vars))
             if len(set(self.dmp_vars)) != len(self.dmp_vars):
                 raise ValueError("dmp: duplicate variable indices %s" % self.dmp_vars)
+        self.conservative_interface = bool(conservative_interface)
+        if self.conservative_interface and self.uses_xt:
+            raise ValueError("conservative_interface=True: the terms depend on position / time; the conservative DG / FV interface is built "
+                             "for term sets of the state alone")
+        if self.conservative_interface and self.ncp_exprs is not None:
+            raise ValueError("conservative_interface=True: the term set carries a non-conservative product; the flux mismatch on a DG / FV "
+                             "face is closed for conservative terms only")
         self._lib = None
         self._id = None
 
@@ -431,6 +445,9 @@ class SympyPDE:
                                "        default:\n            for (int v = 0; v < NV; v++) out[v] = 0.0;\n        }\n    }\n"
                                % ("" if fast else "    static constexpr bool HAS_NCP = true;\n", sig, "\n".join(cases)))
         src_member += self._admissible_member()
+        if self.conservative_interface:
+            src_member += ("    // the a-posteriori subcell limiter's conservative DG / FV interface is built for this term set (exa_lim_conserve.hpp)\n"
+                           "    static constexpr bool HAS_CONSERVATIVE_INTERFACE = true;\n")
         if self.uses_xt:
             fast_cases = ["        case %d: {\n%s\n        } break;" % (d, self._block(self.flux_exprs[d], ["F[%d]" % v for v in range(n)], "            ", fast=True))
                           for d in range(self.max_dim)]
@@ -633,6 +650,9 @@ struct UserPDE {
         if self.adm_exprs is not None:                                 # (the detector unit is built for such term sets only)
             for f in ("lim_user.hip", "exa_lim_detect.hpp"):
                 h.update(open(os.path.join(CSRC, f), "rb").read())
+        if self.conservative_interface:                                # (... and so is the unit of the conservative interface)
+            for f in ("lim_conserve_user.hip", "exa_lim_conserve.hpp", "exa_lim_detect.hpp"):
+                h.update(open(os.path.join(CSRC, f), "rb").read())
         h.update(open(os.path.join(os.path.dirname(os.path.abspath(__file__)), "build.py"), "rb").read())      # (compiler flags)
         h.update(repr(self.dg_flags).encode())
         h.update(os.environ.get("EXA_EXTRA_FLAGS", "").encode())       # (development builds with extra -D macros: a library of their own)
@@ -666,6 +686,8 @@ struct UserPDE {
             units += [("dg_inst.hip", "dg3.o", ["-DEXA_DIM=3", "-DEXA_UNIT_A"] + sched), ("dg_inst.hip", "dg3b.o", ["-DEXA_DIM=3", "-DEXA_UNIT_B"])]
         if self.adm_exprs is not None:                                 # the term set's own a-posteriori detector (exa_user_lim_snapshot / _detect)
             units.append(("lim_user.hip", "lim.o", []))
+        if self.conservative_interface:                                # its instantiation of exa_lim_face_flux / exa_lim_interface_correct
+            units.append(("lim_conserve_user.hip", "limc.o", []))
         procs = [(o, subprocess.Popen(common + extra + ["-c", os.path.join(CSRC, src), "-o", os.path.join(d, o)],
                                       stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, env=_build.compiler_env())) for src, o, extra in units]
         for o, p in procs:

@@ -1364,10 +1364,11 @@ class SubcellLimiter:
             raise ValueError("SubcellLimiter.%s(conservative=True): needs the two-kernel solver step (the face traces of the step in memory, no "
                              "pending corrector); construct the solver with one_kernel_step=False%s" % (who, ", fused_single_stage=False" if s._fused else ""))
         flags = s.lib.exa_pde_flags(int(s.pde))
-        if flags & 3 or (int(s.pde), s.nv) not in ((PDE_EULER, 5), (PDE_ADVECTION, 1)):
-            raise ValueError("SubcellLimiter.%s(conservative=True): built for the built-in Euler (5 variables) and advection (1 variable) term sets; "
-                             "term set %d with %d variables%s is not served" % (who, int(s.pde), s.nv, " (position / time dependent terms or a "
-                                                                                "non-conservative product)" if flags & 3 else ""))
+        # include/exahype_hip.h EXA_PDE_FLAG_XT | EXA_PDE_FLAG_NCP: never served; EXA_PDE_FLAG_CONSERVATIVE (8): a registered set that asked for it
+        if flags & 3 or not (flags & 8 or (int(s.pde), s.nv) in ((PDE_EULER, 5), (PDE_ADVECTION, 1))):
+            raise ValueError("SubcellLimiter.%s(conservative=True): built for the built-in Euler (5 variables) and advection (1 variable) term sets "
+                             "and for term sets generated with SympyPDE(conservative_interface=True); term set %d with %d variables%s is not served"
+                             % (who, int(s.pde), s.nv, " (position / time dependent terms or a non-conservative product)" if flags & 3 else ""))
         self._mask_cum = torch.zeros(tuple(s.nc), dtype=torch.bool, device=s.dev)
         self._fvflux = torch.zeros((self.capacity, s.lib.exa_lim_face_flux_count(s._plan)), dtype=torch.float64, device=s.dev)
 
@@ -1456,7 +1457,7 @@ class SubcellLimiter:
         lifts it: exa_lim_interface_correct), so the neighbour's mean changes by what the troubled cell's mean changed, with the opposite
         sign.  A corrected neighbour can leave the admissible states: the next round detects it.  The capacity holds per round; the return
         value is the number of cells in the cumulative mask.  One block only (ValueError on a partitioned grid: the exchange of face fluxes
-        between blocks is out of scope), built-in Euler / advection term sets only."""
+        between blocks is out of scope); built-in Euler / advection term sets and generated ones with SympyPDE(conservative_interface=True)."""
         s = self.s
         self._one_volume_size("step_a_posteriori")
         self._mood_setup()

@@ -73,10 +73,13 @@ int exa_register_pde(const char* library_path, int* pde_id);
  * coordinates the kernels hand them; exa_pde_eval_device and exa_dg_max_eigenvalue, which have none, evaluate them at x = 0, t = 0:
  * use exa_pde_eval_device_at for the CFL scan of such a term set, as exahype_amd/solvers.py does);
  * EXA_PDE_FLAG_NCP -- it carries a non-conservative product;
- * EXA_PDE_FLAG_ADMISSIBLE -- it says itself what the a-posteriori limiter's detector checks (exa_lim_snapshot / exa_lim_detect below). */
+ * EXA_PDE_FLAG_ADMISSIBLE -- it says itself what the a-posteriori limiter's detector checks (exa_lim_snapshot / exa_lim_detect below);
+ * EXA_PDE_FLAG_CONSERVATIVE -- its side library carries the limiter's conservative DG / FV interface (exa_lim_face_flux /
+ * exa_lim_interface_correct below): pde_codegen.SympyPDE(conservative_interface=True), never together with XT or NCP. */
 #define EXA_PDE_FLAG_XT 1
 #define EXA_PDE_FLAG_NCP 2
 #define EXA_PDE_FLAG_ADMISSIBLE 4
+#define EXA_PDE_FLAG_CONSERVATIVE 8
 int exa_pde_flags(int pde);
 
 /* ---- point-wise PDE terms (Functions.h:2-3) ---------------------------------- */
@@ -322,8 +325,12 @@ int exa_lim_snapshot(exa_dg_plan* plan, const double* u_dev, double* u_old_dev, 
 int exa_lim_detect(exa_dg_plan* plan, const double* u_cand_dev, const double* bounds_dev, const double* const* ghost_bounds_dev,
                    const int* face_kind, double d0, double eps, double floor, unsigned char* mask_dev, void* stream);
 /* Conservative DG / FV interface for the a-posteriori limiter.  A troubled cell is redone with the FV patch update, its untroubled
- * face neighbour keeps the DG corrector: on their common face the two used different fluxes.  Built-in Euler (5 variables) and advection
- * (1 variable) term sets; EXA_PDE_FLAG_XT / EXA_PDE_FLAG_NCP and registered term sets return EXA_ERR_INVALID.  -1 slots are skipped.
+ * face neighbour keeps the DG corrector: on their common face the two used different fluxes.  Served: the built-in Euler (5 variables)
+ * and advection (1 variable) term sets, and a registered term set with EXA_PDE_FLAG_CONSERVATIVE
+ * (pde_codegen.SympyPDE(conservative_interface=True)): both entries then dispatch to kernels in its side library, same arithmetic with
+ * its flux and eigenvalue (a source term does not enter a face flux).  EXA_PDE_FLAG_XT / EXA_PDE_FLAG_NCP term sets and registered term
+ * sets without the flag return EXA_ERR_INVALID; so does a variable count / order whose kernel exceeds the 64 KB of LDS a workgroup may
+ * declare (3-D N = 8 from 24 variables).  -1 slots are skipped.
  * exa_lim_face_flux: BEFORE the in-place FV update of the patches (exa_fv_time_step_device overwrites their boundary layers): for each
  *   listed patch and each of its 2*dim faces the corrected-mode Rusanov flux g = (f_d(Q-) + f_d(Q+)) / 2 - max(l_d(Q-), l_d(Q+)) (Q+ - Q-) / 2
  *   between the boundary layer and the halo layer on the N_s^(dim-1) subfaces (Q-: the lower index along d), brought to the N^(dim-1) face
