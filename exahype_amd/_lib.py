@@ -10,7 +10,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(HERE, "lib", "libexahype_hip.so")
 
 PDE_EULER_REF2D, PDE_EULER, PDE_ADVECTION = 0, 1, 2
-FV_FAITHFUL, FV_RUSANOV = 0, 1
+FV_FAITHFUL, FV_RUSANOV, FV_MUSCL_HANCOCK = 0, 1, 2         # include/exahype_hip.h EXA_FV_*
 FV_FACE_PERIODIC, FV_FACE_STATE, FV_FACE_MIRROR = 0, 1, 2      # include/exahype_hip.h EXA_FV_FACE_*
 
 # every symbol include/exahype_hip.h declares: (restype, argtypes)

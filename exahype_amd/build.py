@@ -33,6 +33,8 @@ UNITS = [
     ("dg_operators_host.cpp", "dg_operators_host", ["-x", "hip"]),
     # bit-exact with the g++ build of the reference: no FMA contraction in the FV unit
     ("fv_rusanov.hip", "fv_rusanov", ["-ffp-contract=off"]),
+    # the second-order FV unit: the same arithmetic on both sides of a face and in both of its phases -- no contraction here either
+    ("fv_muscl.hip", "fv_muscl", ["-ffp-contract=off"]),
     ("limiter.hip", "limiter", []),
 ] + [
     unit

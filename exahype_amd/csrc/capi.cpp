@@ -52,6 +52,8 @@ struct UserPde {
     int (*lim_flux)(int, int, const double*, const long*, long, double*, const double*, void*);
     int (*lim_corr)(int, int, const long*, double*, const double*, const long*, long, const unsigned char*, const int*, const double*, double, const double*,
                     const double*, const double*, const double*, void*);
+    // the term set's instantiation of the MUSCL-Hancock patch update (EXA_PDE_FLAG_MUSCL_HANCOCK; fv_muscl_user.hip)
+    int (*fvm)(int, int, int, int, int, long, double*, double, double, const long*, void*, double*);
 };
 static std::vector<UserPde> g_user;
 
@@ -59,6 +61,11 @@ int user_fv_launch(int pde, int mode, int dim, int P, int H, int n_real, int n_a
                    double h, const long* slot, hipStream_t s, double* out, const double* centre, double t, const FvGridArgs* grid) {
     if (pde - 100 >= (int)g_user.size() || !g_user[pde - 100].fv) { set_error("pde %d is not registered", pde); return -1; }
     return g_user[pde - 100].fv(mode, dim, P, H, n_real, n_aux, n_patches, Q, dt, h, slot, (void*)s, out, centre, t, grid);
+}
+int user_fv_muscl_launch(int pde, int dim, int P, int H, int n_real, int n_aux, long n_patches, double* Q, double dt, double h, const long* slot,
+                         hipStream_t s, double* out) {
+    if (pde - 100 >= (int)g_user.size() || !g_user[pde - 100].fvm) { set_error("pde %d carries no MUSCL-Hancock kernel", pde); return -1; }
+    return g_user[pde - 100].fvm(dim, P, H, n_real, n_aux, n_patches, Q, dt, h, slot, (void*)s, out);
 }
 int user_fv_maxeig(int pde, int dim, int P, int H, int n_real, int n_aux, long n_patches, const double* Q, double* lam, hipStream_t s,
                    const double* centre, double t, double h) {
@@ -167,6 +174,14 @@ int exa_register_pde(const char* library_path, int* pde_id) {
             return EXA_ERR_INVALID;
         }
     }
+    if (u.flags & EXA_PDE_FLAG_MUSCL_HANCOCK) {
+        u.fvm = (decltype(u.fvm))dlsym(h, "exa_user_fv_muscl_launch");
+        if (!u.fvm) {
+            dlclose(h);
+            set_error("%s asks for the MUSCL-Hancock patch update but exports no exa_user_fv_muscl_launch", library_path);
+            return EXA_ERR_INVALID;
+        }
+    }
     g_user.push_back(u);
     *pde_id = 100 + (int)g_user.size() - 1;
     return EXA_OK;
@@ -207,7 +222,8 @@ int exa_fv_plan_create(int device, int mode, int dim, int patch_size, int halo_s
     if ((dim != 2 && dim != 3) || patch_size < 1 || halo_size < 0) { set_error("check viability of inputs"); return EXA_ERR_INVALID; }
     // ... plus what the 3-point stencil itself needs
     if (halo_size < 1) { set_error("the Rusanov stencil reads one halo layer: halo_size must be >= 1"); return EXA_ERR_INVALID; }
-    if (mode != EXA_FV_FAITHFUL && mode != EXA_FV_RUSANOV) { set_error("unknown FV mode %d", mode); return EXA_ERR_INVALID; }
+    if (mode != EXA_FV_FAITHFUL && mode != EXA_FV_RUSANOV && mode != EXA_FV_MUSCL_HANCOCK) { set_error("unknown FV mode %d", mode); return EXA_ERR_INVALID; }
+    if (mode == EXA_FV_MUSCL_HANCOCK && halo_size < 2) { set_error("MUSCL-Hancock reads two halo layers: halo_size must be >= 2"); return EXA_ERR_INVALID; }
     if (n_real < 1 || n_real > 8 || n_aux < 0 || n_patches < 0) { set_error("n_real must be 1..8, n_aux >= 0, n_patches >= 0"); return EXA_ERR_INVALID; }
     if (pde == EXA_PDE_EULER_REF2D && (dim != 2 || n_real < 4)) { set_error("EULER_REF2D is the reference's 2-D term set (n_real >= 4)"); return EXA_ERR_INVALID; }
     if (pde == EXA_PDE_EULER && n_real < 5) { set_error("EULER needs n_real >= 5"); return EXA_ERR_INVALID; }
@@ -215,8 +231,25 @@ int exa_fv_plan_create(int device, int mode, int dim, int patch_size, int halo_s
         if (pde - 100 >= (int)g_user.size()) { set_error("pde %d is not registered", pde); return EXA_ERR_INVALID; }
         if (n_real < g_user[pde - 100].nv) { set_error("pde %d evolves %d variables; n_real = %d", pde, g_user[pde - 100].nv, n_real); return EXA_ERR_INVALID; }
     } else if (pde < 0 || pde > 2) { set_error("unknown pde %d", pde); return EXA_ERR_INVALID; }
+    if (mode == EXA_FV_MUSCL_HANCOCK) {
+        if (pde == EXA_PDE_EULER_REF2D) {
+            set_error("EXA_FV_MUSCL_HANCOCK: EULER_REF2D is the reference's quirk set (F[4] is never written); use EXA_PDE_EULER");
+            return EXA_ERR_INVALID;
+        }
+        if (pde >= 100 && !(g_user[pde - 100].flags & EXA_PDE_FLAG_MUSCL_HANCOCK)) {
+            set_error("EXA_FV_MUSCL_HANCOCK: pde %d was generated without the MUSCL-Hancock kernel; build it with SympyPDE(..., muscl_hancock=True)", pde);
+            return EXA_ERR_INVALID;
+        }
+        FvMusclPlan pl;
+        if (patch_size > 1024 || !fv_muscl_plan(dim, patch_size, n_real, n_real + n_aux, &pl)) {
+            if (patch_size > 1024) pl.lds = (size_t)-1;
+            set_error("EXA_FV_MUSCL_HANCOCK: a patch of %d^%d volumes with %d + %d variables needs %zu bytes of LDS (window and predictor), %zu bytes are "
+                      "available", patch_size, dim, n_real, n_aux, pl.lds, FV_MUSCL_LDS_AVAILABLE);
+            return EXA_ERR_INVALID;
+        }
+    }
     const long ncell = lpow(patch_size, dim);
-    if (ncell > 4096) { set_error("FV patch with %ld volumes exceeds the 4096 a workgroup keeps in registers", ncell); return EXA_ERR_INVALID; }
+    if (mode != EXA_FV_MUSCL_HANCOCK && ncell > 4096) { set_error("FV patch with %ld volumes exceeds the 4096 a workgroup keeps in registers", ncell); return EXA_ERR_INVALID; }
     int rc = use_device(device);
     if (rc) return rc;
     exa_fv_plan* p = new (std::nothrow) exa_fv_plan;
@@ -232,11 +265,18 @@ int exa_fv_plan_destroy(exa_fv_plan* plan) { delete plan; return EXA_OK; }
 
 long exa_fv_q_count(const exa_fv_plan* plan) { return plan ? plan->count : 0; }
 
+// the second-order update of a plan in mode EXA_FV_MUSCL_HANCOCK (its term sets see the state alone: no centres, no time)
+static int fv_muscl(exa_fv_plan* p, double* Q_dev, double dt, double h, const long* slot_dev, void* stream, double* out_dev) {
+    return fv_muscl_launch(p->dim, p->P, p->H, p->n_real, p->n_aux, p->n_patches, p->pde, Q_dev, dt, h, slot_dev, (hipStream_t)stream, out_dev);
+}
+
 int exa_fv_time_step_device_masked(exa_fv_plan* p, double* Q_dev, const long* slot_dev, double dt, double h, void* stream) {
     if (!p || (!Q_dev && p->count > 0)) { set_error("exa_fv_time_step_device: NULL argument"); return EXA_ERR_INVALID; }
     if (p->mode == EXA_FV_RUSANOV && !(h > 0.0)) { set_error("EXA_FV_RUSANOV needs the volume size h > 0"); return EXA_ERR_INVALID; }
+    if (p->mode == EXA_FV_MUSCL_HANCOCK && !(h > 0.0)) { set_error("EXA_FV_MUSCL_HANCOCK needs the volume size h > 0"); return EXA_ERR_INVALID; }
     int rc = use_device(p->device);
     if (rc) return rc;
+    if (p->mode == EXA_FV_MUSCL_HANCOCK) return fv_muscl(p, Q_dev, dt, h, slot_dev, stream, nullptr);
     return fv_launch(p->mode, p->dim, p->P, p->H, p->n_real, p->n_aux, p->n_patches, p->pde, Q_dev, dt, h, slot_dev, (hipStream_t)stream);
 }
 
@@ -246,6 +286,7 @@ int exa_fv_time_step_device_masked_at(exa_fv_plan* p, double* Q_dev, const long*
     if (!(h > 0.0)) { set_error("exa_fv_time_step_device_masked_at needs the volume size h > 0 (volume centres, dt / h)"); return EXA_ERR_INVALID; }
     int rc = use_device(p->device);
     if (rc) return rc;
+    if (p->mode == EXA_FV_MUSCL_HANCOCK) return fv_muscl(p, Q_dev, dt, h, slot_dev, stream, nullptr);
     return fv_launch(p->mode, p->dim, p->P, p->H, p->n_real, p->n_aux, p->n_patches, p->pde, Q_dev, dt, h, slot_dev, (hipStream_t)stream, nullptr,
                      centre_dev, t);
 }
@@ -256,6 +297,7 @@ int exa_fv_time_step_device_oop(exa_fv_plan* p, const double* QIn_dev, double* Q
     if (!(h > 0.0)) { set_error("exa_fv_time_step_device_oop needs the volume size h > 0 (volume centres, dt / h)"); return EXA_ERR_INVALID; }
     int rc = use_device(p->device);
     if (rc) return rc;
+    if (p->mode == EXA_FV_MUSCL_HANCOCK) return fv_muscl(p, const_cast<double*>(QIn_dev), dt, h, nullptr, stream, QOut_dev);
     // (the kernel only reads QIn: the const is cast away for the signature it shares with the in-place call)
     return fv_launch(p->mode, p->dim, p->P, p->H, p->n_real, p->n_aux, p->n_patches, p->pde, const_cast<double*>(QIn_dev), dt, h, nullptr,
                      (hipStream_t)stream, QOut_dev, centre_dev, t);
@@ -266,6 +308,7 @@ int exa_fv_time_step_device_at(exa_fv_plan* p, double* Q_dev, const double* cent
     if (!(h > 0.0)) { set_error("exa_fv_time_step_device_at needs the volume size h > 0 (volume centres, dt / h)"); return EXA_ERR_INVALID; }
     int rc = use_device(p->device);
     if (rc) return rc;
+    if (p->mode == EXA_FV_MUSCL_HANCOCK) return fv_muscl(p, Q_dev, dt, h, nullptr, stream, nullptr);
     return fv_launch(p->mode, p->dim, p->P, p->H, p->n_real, p->n_aux, p->n_patches, p->pde, Q_dev, dt, h, nullptr, (hipStream_t)stream, nullptr,
                      centre_dev, t);
 }
@@ -274,6 +317,11 @@ int exa_fv_time_step_device_at(exa_fv_plan* p, double* Q_dev, const double* cent
 static int fv_grid_step(const char* who, exa_fv_plan* p, const double* Q_dev, double* QNext_dev, const long* grid, const int* face_kind, const double* face_data_dev,
                         const double* centre_dev, double t, double dt, double h, double* lambda_next_dev, void* stream) {
     if (!p || !grid || ((!Q_dev || !QNext_dev) && p->count > 0)) { set_error("%s: NULL argument", who); return EXA_ERR_INVALID; }
+    if (p->mode == EXA_FV_MUSCL_HANCOCK) {
+        set_error("%s: the one-launch grid step takes its halo states from the face neighbours only; EXA_FV_MUSCL_HANCOCK needs the edge neighbours "
+                  "(diagonal patches) too -- fill the halos of the array with halo and call exa_fv_time_step_device", who);
+        return EXA_ERR_INVALID;
+    }
     if (Q_dev == QNext_dev) { set_error("%s: the new states need an array of their own (the neighbours read the old ones)", who); return EXA_ERR_INVALID; }
     if (p->mode == EXA_FV_RUSANOV && !(h > 0.0)) { set_error("%s: EXA_FV_RUSANOV needs the volume size h > 0", who); return EXA_ERR_INVALID; }
     FvGridArgs ga{QNext_dev, nullptr, {1, 1, 1}, lambda_next_dev, {0, 0, 0, 0, 0, 0}};

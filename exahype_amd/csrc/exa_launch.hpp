@@ -108,6 +108,36 @@ int user_fv_maxeig(int pde, int dim, int P, int H, int n_real, int n_aux, long n
                    const double* centre, double t, double h);
 int user_pde_eval(int pde, int normal, long n, int stride, const double* Q, double* F, double* lam, hipStream_t s, const double* X, double t);
 
+// fv_muscl.hip (exa_fv_muscl.hpp): the second-order MUSCL-Hancock patch update, EXA_FV_MUSCL_HANCOCK.  Its LDS plan: per patch the window
+// (P + 4)^dim x V and the predictor's increments (P + 2)^dim x n_real, 8 B each; patches whose plan stays within 64 KiB share a 256-thread
+// workgroup (as many as have a volume per thread), a larger one has a workgroup to itself (2-D above 80 KiB: 512 threads, since only one such
+// workgroup fits a CU; the 3-D kernels need more than the 256 registers a lane of a 512-thread workgroup has).  -> false: one patch does not fit (pl->lds = the bytes it needs); exa_fv_plan_create refuses such a shape.
+constexpr size_t FV_MUSCL_LDS_AVAILABLE = 160 * 1024;
+struct FvMusclPlan {
+    int ppb, nt;
+    size_t lds;
+};
+inline bool fv_muscl_plan(int dim, int P, int n_real, int V, FvMusclPlan* pl) {
+    const size_t T = (size_t)P + 4, D = (size_t)P + 2;
+    const size_t per = ((dim == 3 ? T * T * T : T * T) * (size_t)V + (dim == 3 ? D * D * D : D * D) * (size_t)n_real) * sizeof(double);
+    const size_t ncell = dim == 3 ? (size_t)P * P * P : (size_t)P * P;
+    pl->ppb = 1;
+    pl->lds = per;
+    pl->nt = (dim == 2 && per > 80 * 1024) ? 512 : 256;
+    if (per > FV_MUSCL_LDS_AVAILABLE) return false;
+    if (ncell <= 256 && 2 * per <= 64 * 1024) {
+        const size_t by_threads = 256 / ncell, by_lds = 64 * 1024 / per;
+        pl->ppb = (int)(by_threads < by_lds ? by_threads : by_lds);
+        pl->lds = per * pl->ppb;
+    }
+    return true;
+}
+// out != nullptr: out of place (QOut halo-less); slot: as fv_launch
+int fv_muscl_launch(int dim, int P, int H, int n_real, int n_aux, long n_patches, int pde, double* Q, double dt, double h, const long* slot,
+                    hipStream_t s, double* out);
+int user_fv_muscl_launch(int pde, int dim, int P, int H, int n_real, int n_aux, long n_patches, double* Q, double dt, double h, const long* slot,
+                         hipStream_t s, double* out);
+
 void set_error(const char* fmt, ...);
 
 }  // namespace exa

@@ -86,6 +86,12 @@ template <class P> struct pde_has_admissible<P, std::void_t<decltype(P::HAS_ADMI
 // flux_rt / maxeig.  pde_codegen.SympyPDE(conservative_interface=True) generates the marker.
 template <class P, class = void> struct pde_has_conservative_interface : std::false_type {};
 template <class P> struct pde_has_conservative_interface<P, std::void_t<decltype(P::HAS_CONSERVATIVE_INTERFACE)>> : std::bool_constant<P::HAS_CONSERVATIVE_INTERFACE> {};
+// Optional: `static constexpr bool HAS_MUSCL_HANCOCK = true` -- the term set asks for the second-order MUSCL-Hancock patch update
+// (exa_fv_muscl.hpp, EXA_FV_MUSCL_HANCOCK): its side library then carries its own instantiation (fv_muscl_user.hip).  Only for conservative
+// term sets of the state alone (no source, no non-conservative product): slopes, predictor and face flux use flux_rt / maxeig.
+// pde_codegen.SympyPDE(muscl_hancock=True) generates the marker.
+template <class P, class = void> struct pde_has_muscl_hancock : std::false_type {};
+template <class P> struct pde_has_muscl_hancock<P, std::void_t<decltype(P::HAS_MUSCL_HANCOCK)>> : std::bool_constant<P::HAS_MUSCL_HANCOCK> {};
 
 // The same terms for the ADER-DG kernels (tolerance 1e-10): generated term sets carry `_fast` twins whose reciprocals / square roots use the
 // fast sequences below (pde_codegen.py); a term set without them is evaluated as it is.

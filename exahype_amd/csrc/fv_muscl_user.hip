@@ -1,0 +1,21 @@
+// MUSCL-Hancock patch update (exa_fv_muscl.hpp) for a generated term set: the unit a side library carries when the term set was built with
+// pde_codegen.SympyPDE(..., muscl_hancock=True) (HAS_MUSCL_HANCOCK; exa_register_pde resolves exa_user_fv_muscl_launch).
+#include EXA_USER_PDE_HEADER      // struct exa::UserPDE
+#include "exa_fv_muscl.hpp"
+
+static_assert(exa::pde_has_muscl_hancock<exa::UserPDE>::value, "fv_muscl_user.hip is built for term sets generated with muscl_hancock=True");
+static_assert(!exa::pde_has_xt<exa::UserPDE>::value && !exa::pde_has_ncp<exa::UserPDE>::value && !exa::pde_has_source<exa::UserPDE>::value,
+              "MUSCL-Hancock: conservative terms of the state alone");
+
+extern "C" int exa_user_fv_muscl_launch(int dim, int P, int H, int n_real, int n_aux, long n_patches, double* Q, double dt, double h, const long* slot,
+                                        void* stream, double* out) {
+    using namespace exa;
+    const int V = n_real + n_aux;
+    if (n_real > FVM_MAXV || n_real < UserPDE::NV) { set_error("user PDE evolves %d variables; n_real = %d", UserPDE::NV, n_real); return -1; }
+    if (dim == 2) return fv_muscl_run<2, UserPDE>(P, H, n_real, V, n_patches, Q, dt, h, slot, (hipStream_t)stream, out);
+    if constexpr (UserPDE::MAXDIM >= 3) {
+        if (dim == 3) return fv_muscl_run<3, UserPDE>(P, H, n_real, V, n_patches, Q, dt, h, slot, (hipStream_t)stream, out);
+    }
+    set_error("user PDE: no MUSCL-Hancock kernel for dim %d", dim);
+    return -1;
+}

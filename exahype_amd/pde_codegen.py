@@ -118,7 +118,7 @@ def _arity(fn):
 
 class SympyPDE:
     def __init__(self, n_vars, flux, max_eigenvalue, max_dim=3, name="user", source=None, ncp=None, max_aux=None, admissible=None, dmp=None, *,
-                 conservative_interface=False):
+                 conservative_interface=False, muscl_hancock=False):
         """flux(q, d) -> n_vars expressions, max_eigenvalue(q, d) -> one, in the state symbols q; d = 0-based normal.
         source(q) -> n_vars expressions (optional): the algebraic source S(q) of q_t + div F(q) = S(q) -- the hook the
         reference's harness declares beside flux and maxEigenvalue (`Unit test/correctness_test.cpp:16-23`).  It enters the
@@ -149,7 +149,14 @@ class SympyPDE:
         (SubcellLimiter.step / step_a_posteriori / run with conservative=True).  The generated struct then carries HAS_CONSERVATIVE_INTERFACE and
         the side library its own instantiation of the two interface kernels (csrc/lim_conserve_user.hip): the FV face flux is the Rusanov
         flux of flux / max_eigenvalue, which a source term does not enter.  Not for terms that depend on position / time and not together
-        with an ncp (ValueError); without the keyword the generated source is what it was."""
+        with an ncp (ValueError); without the keyword the generated source is what it was.
+
+        muscl_hancock=True (keyword only): the term set asks for the second-order MUSCL-Hancock patch update (FVRusanovKernel / FVPatchGrid /
+        HIPPrinter with mode FV_MUSCL_HANCOCK).  The generated struct then carries HAS_MUSCL_HANCOCK and the side library one more unit
+        (csrc/fv_muscl_user.hip, exa_user_fv_muscl_launch).  The scheme -- slopes, half-step predictor, Rusanov flux of the predicted face
+        states -- is written for conservative terms of the state alone: terms that depend on position / time, an ncp or a source raise
+        ValueError.  Without the keyword the generated source, the cache key and the build are what they were, and a plan in that mode on such a
+        term set is refused."""
         if not 1 <= n_vars <= 8:
             raise ValueError("n_vars must be 1..8")
         self.n_vars, self.max_dim, self.name = n_vars, max_dim, name
@@ -210,6 +217,14 @@ class SympyPDE:
         if self.conservative_interface and self.ncp_exprs is not None:
             raise ValueError("conservative_interface=True: the term set carries a non-conservative product; the flux mismatch on a DG / FV "
                              "face is closed for conservative terms only")
+        self.muscl_hancock = bool(muscl_hancock)
+        if self.muscl_hancock and self.uses_xt:
+            raise ValueError("muscl_hancock=True: the terms depend on position / time; the MUSCL-Hancock update is built for term sets of the "
+                             "state alone")
+        if self.muscl_hancock and self.ncp_exprs is not None:
+            raise ValueError("muscl_hancock=True: the term set carries a non-conservative product; the MUSCL-Hancock update has no place for it yet")
+        if self.muscl_hancock and self.source_exprs is not None:
+            raise ValueError("muscl_hancock=True: the term set carries a source term; the MUSCL-Hancock update has no place for it yet")
         self._lib = None
         self._id = None
 
@@ -448,6 +463,9 @@ class SympyPDE:
         if self.conservative_interface:
             src_member += ("    // the a-posteriori subcell limiter's conservative DG / FV interface is built for this term set (exa_lim_conserve.hpp)\n"
                            "    static constexpr bool HAS_CONSERVATIVE_INTERFACE = true;\n")
+        if self.muscl_hancock:
+            src_member += ("    // the second-order MUSCL-Hancock patch update is built for this term set (exa_fv_muscl.hpp)\n"
+                           "    static constexpr bool HAS_MUSCL_HANCOCK = true;\n")
         if self.uses_xt:
             fast_cases = ["        case %d: {\n%s\n        } break;" % (d, self._block(self.flux_exprs[d], ["F[%d]" % v for v in range(n)], "            ", fast=True))
                           for d in range(self.max_dim)]
@@ -653,6 +671,9 @@ struct UserPDE {
         if self.conservative_interface:                                # (... and so is the unit of the conservative interface)
             for f in ("lim_conserve_user.hip", "exa_lim_conserve.hpp", "exa_lim_detect.hpp"):
                 h.update(open(os.path.join(CSRC, f), "rb").read())
+        if self.muscl_hancock:                                         # (... and the unit of the second-order patch update)
+            for f in ("fv_muscl_user.hip", "exa_fv_muscl.hpp"):
+                h.update(open(os.path.join(CSRC, f), "rb").read())
         h.update(open(os.path.join(os.path.dirname(os.path.abspath(__file__)), "build.py"), "rb").read())      # (compiler flags)
         h.update(repr(self.dg_flags).encode())
         h.update(os.environ.get("EXA_EXTRA_FLAGS", "").encode())       # (development builds with extra -D macros: a library of their own)
@@ -688,6 +709,8 @@ struct UserPDE {
             units.append(("lim_user.hip", "lim.o", []))
         if self.conservative_interface:                                # its instantiation of exa_lim_face_flux / exa_lim_interface_correct
             units.append(("lim_conserve_user.hip", "limc.o", []))
+        if self.muscl_hancock:                                         # its instantiation of the MUSCL-Hancock patch update (exa_user_fv_muscl_launch)
+            units.append(("fv_muscl_user.hip", "fvm.o", ["-ffp-contract=off"]))
         procs = [(o, subprocess.Popen(common + extra + ["-c", os.path.join(CSRC, src), "-o", os.path.join(d, o)],
                                       stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, env=_build.compiler_env())) for src, o, extra in units]
         for o, p in procs:

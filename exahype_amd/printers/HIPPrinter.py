@@ -15,6 +15,10 @@ Recognised schemes
                          of the generated `Unit test/test.cpp`.
   "fv-rusanov"           same declarations, corrected Rusanov update (dt/h, all
                          n_real variables) -- explicit hint only.
+  "fv-muscl-hancock"     same declarations on a builder with halo_size >= 2, second-order
+                         MUSCL-Hancock update (minmod slopes, unsplit half-step predictor,
+                         Rusanov flux of the predicted face states; it reads the edge
+                         entries of the halo) -- explicit hint only.
   "aderdg"               ADER-DG step on cells = patches (patch_size = order+1,
                          halo_size = 0, n_patches = number of cells) -- explicit
                          hint only; not expressible in the reference's surface.
@@ -184,7 +188,7 @@ class HIPPrinter(CodePrinter):
                              % (function_name, len(k.LHS), len(self.lowering.statements))) + self.lowering.source()
                 return
             scheme = "fv-rusanov-faithful"
-        if scheme not in ("fv-rusanov-faithful", "fv-rusanov", "aderdg"):
+        if scheme not in ("fv-rusanov-faithful", "fv-rusanov", "fv-muscl-hancock", "aderdg"):
             raise ValueError("unknown scheme %r" % scheme)
         self.scheme = scheme
         # The PDE terms are opaque symbols in the reference (resolved at link time to the user's C++, Functions.h:2-4); a
@@ -228,6 +232,8 @@ class HIPPrinter(CodePrinter):
             self.grid = grid
         elif k.halo_size < 1:
             raise ValueError("the Rusanov stencil reads one halo layer: halo_size must be >= 1")
+        elif scheme == "fv-muscl-hancock" and k.halo_size < 2:
+            raise ValueError("scheme='fv-muscl-hancock' reads two halo layers: halo_size must be >= 2")
         self.code = self._plan_text()
 
     # -- inspection --------------------------------------------------------------------------------
@@ -282,7 +288,7 @@ class HIPPrinter(CodePrinter):
                   % (k.dim, N, k.n_real, self.pde, self.n_picard, ",".join(map(str, self.grid))),
                   "// arrays     : u[%d][%s][%d] fp64, AoS (reference layout), updated in place" % (k.n_patches, "][".join([str(N)] * k.dim), k.n_real)]
         else:
-            mode = 0 if self.scheme == "fv-rusanov-faithful" else 1
+            mode = {"fv-rusanov-faithful": 0, "fv-rusanov": 1, "fv-muscl-hancock": 2}[self.scheme]
             if self.cell_data:
                 L += ["// flavour    : exahype2::CellData (examples/kernel-generator.py): %s with halo is read, %s (halo-less) is written; the"
                       % (k.items[2], k.items[1]),
@@ -290,8 +296,12 @@ class HIPPrinter(CodePrinter):
                       "//              function): the corrected Rusanov update it stands for is dispatched, out of place",
                       "// C-ABI      : exa_fv_time_step_device_oop(plan, %s, %s, cellCentre, t, dt, h = cellSize / patch_size, stream)"
                       % (k.items[2], k.items[1])]
-            L += ["// kernel     : fv_rusanov_kernel<%d, mode %d> -- %d statements fused into one launch, one workgroup per patch"
-                  % (k.dim, mode, len(k.LHS)),
+            L += ["// kernel     : fv_muscl_kernel<%d> (EXA_FV_MUSCL_HANCOCK) -- slopes and half-step predictor, then the Rusanov flux of the predicted face states,"
+                  % k.dim,
+                  "//              one launch; reads two halo layers and their edge entries"] if mode == 2 else [
+                  "// kernel     : fv_rusanov_kernel<%d, mode %d> -- %d statements fused into one launch, one workgroup per patch"
+                  % (k.dim, mode, len(k.LHS))]
+            L += [
                   "// C-ABI      : exa_fv_plan_create(dev, %d, %d, %d, %d, %d, %d, %d, %d, &plan); exa_fv_time_step_device(plan, %s, %s, h, stream)"
                   % (mode, k.dim, k.patch_size, k.halo_size, k.n_real, k.n_aux, k.n_patches, self.pde, k.items[0] if k.items else "Q",
                      k.inputs[0] if k.inputs else "dt"),
@@ -338,7 +348,7 @@ class HIPPrinter(CodePrinter):
                                                   n_picard=self.n_picard, device=self.device)
                 self.code = self._plan_text(stage_a=self._impl.stage_a_kernel_name())     # the plan's own word for its stage A
             else:
-                mode = solvers.FV_FAITHFUL if self.scheme == "fv-rusanov-faithful" else solvers.FV_RUSANOV
+                mode = {"fv-rusanov-faithful": solvers.FV_FAITHFUL, "fv-rusanov": solvers.FV_RUSANOV, "fv-muscl-hancock": solvers.FV_MUSCL_HANCOCK}[self.scheme]
                 self._impl = solvers.FVRusanovKernel(k.dim, k.patch_size, k.halo_size, k.n_real, k.n_aux, k.n_patches,
                                                      pde=self.pde, mode=mode, device=self.device)
         return self._impl

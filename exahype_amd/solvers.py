@@ -14,7 +14,7 @@ import os
 import numpy as np
 
 from . import _lib
-from ._lib import (FV_FAITHFUL, FV_RUSANOV, PDE_ADVECTION, PDE_EULER, PDE_EULER_REF2D, check, darr, larr)
+from ._lib import (FV_FAITHFUL, FV_MUSCL_HANCOCK, FV_RUSANOV, PDE_ADVECTION, PDE_EULER, PDE_EULER_REF2D, check, darr, larr)
 from .boundary import Dirichlet, Outflow, Wall, coefficients as _bc_coefficients, fv_faces as _fv_faces, validate_boundary
 
 
@@ -33,7 +33,13 @@ def _stream_ptr():
 # ----------------------------------------------------------------------------------------------
 class FVRusanovKernel:
     """`time_step(Q, dt)` on MI355X for `n_patches` patches of the reference layout
-    Q[patch][i][j]([k])[var] (halo included)."""
+    Q[patch][i][j]([k])[var] (halo included).
+
+    mode: FV_FAITHFUL (the reference's statement list), FV_RUSANOV (the corrected first-order update) or FV_MUSCL_HANCOCK -- second order:
+    minmod slopes, an unsplit half-step predictor, the Rusanov flux of the predicted face states (exahype_amd/csrc/exa_fv_muscl.hpp).  That
+    mode needs halo_size >= 2 and reads the EDGE entries of the two halo layers next to the interior (layer 1 along two axes) beside the
+    face entries; it serves PDE_EULER, PDE_ADVECTION and term sets generated with SympyPDE(..., muscl_hancock=True), ignores `centres` / `t`,
+    and a patch whose LDS plan does not fit a compute unit is refused when the kernel object is created."""
 
     def __init__(self, dim, patch_size, halo_size, n_real, n_aux, n_patches=1, pde=PDE_EULER_REF2D,
                  mode=FV_FAITHFUL, device=0):
@@ -883,7 +889,17 @@ class FVPatchGrid:
     def __init__(self, dim, grid, patch_size, halo_size=1, n_real=5, n_aux=0, pde=PDE_EULER, mode=FV_RUSANOV,
                  length=1.0, device=0, boundary=None, origin=None, time=0.0, fused=True):
         """origin, time: physical coordinates of the grid's low corner and the start time -- reach term sets whose terms depend on position /
-        time (the patch centres follow from them); step() / run() advance the time."""
+        time (the patch centres follow from them); step() / run() advance the time.
+
+        mode=FV_MUSCL_HANCOCK (second order) runs with halo_size >= 2 and fused=False only: its stencil reads the edge entries of the halo,
+        which belong to diagonal patches -- the halo fills of the two-pass form supply them, the one-launch step takes face neighbours only."""
+        if mode == FV_MUSCL_HANCOCK:
+            if halo_size < 2:
+                raise ValueError("FVPatchGrid(mode=FV_MUSCL_HANCOCK): the scheme reads two halo layers, halo_size must be >= 2 (got %d)" % halo_size)
+            if fused:
+                raise ValueError("FVPatchGrid(mode=FV_MUSCL_HANCOCK) needs fused=False: the one-launch grid step takes its halo states from the face "
+                                 "neighbours only, this scheme also reads the edge entries (diagonal patches); the two-pass form on the array with "
+                                 "halo fills them")
         torch = _torch()
         self.dim, self.grid, self.P, self.H = dim, tuple(int(g) for g in grid), patch_size, halo_size
         self.n_real, self.n_aux, self.pde = n_real, n_aux, pde

@@ -55,6 +55,22 @@ extern "C" {
 /* FV Rusanov patch-update modes */
 #define EXA_FV_FAITHFUL 0        /* Unit test/test.cpp:11-104 statement for statement (zero-initialised temporaries) */
 #define EXA_FV_RUSANOV 1         /* corrected Rusanov: dt/h, all n_real variables, dissipative sign */
+/* Second order: minmod slopes per axis, an unsplit half-step predictor over all axes, the Rusanov flux of the predicted face states (the
+ * scheme, statement by statement: exahype_amd/csrc/exa_fv_muscl.hpp).
+ *   - halo_size >= 2.  An interior update reads Q at c +- e_d, c +- 2 e_d and c +- e_d +- e_e (d != e): the two halo layers next to the
+ *     interior INCLUDING the edge entries (layer 1 along two axes) -- a caller that fills halos fills those too.  It never reads the entries at
+ *     (+-2, +-1), the 3-D corner entries or a layer beyond the second.
+ *   - served by exa_fv_time_step_host / _device / _device_masked / _device_oop and by _device_at / _device_masked_at (centres and t are
+ *     ignored: the term sets of this mode see the state alone); h > 0 is required, as for EXA_FV_RUSANOV.
+ *   - term sets: EXA_PDE_EULER, EXA_PDE_ADVECTION and registered ones with EXA_PDE_FLAG_MUSCL_HANCOCK.  EXA_PDE_EULER_REF2D (F[4] never
+ *     written) is refused.
+ *   - exa_fv_plan_create refuses (EXA_ERR_INVALID) a shape whose LDS plan -- 8 ((patch_size + 4)^dim (n_real + n_aux) + (patch_size + 2)^dim
+ *     n_real) bytes for one patch -- exceeds the 160 KiB of a compute unit; the message names both figures.  Served: 2-D patch_size <= 32
+ *     with 5 variables, <= 20 with 10; 3-D patch_size <= 8 with up to 6.  Larger 3-D patches would need plane streaming: not built.
+ *   - exa_fv_grid_step_device[_bc] return EXA_ERR_INVALID: the one-launch grid step takes face neighbours only, this scheme needs the edge
+ *     neighbours (diagonal patches); fill the halos of the array with halo and call exa_fv_time_step_device.
+ *   - exa_fv_max_eigenvalue serves plans of this mode as it serves the others. */
+#define EXA_FV_MUSCL_HANCOCK 2
 
 typedef struct exa_fv_plan exa_fv_plan;
 typedef struct exa_dg_plan exa_dg_plan;
@@ -75,11 +91,14 @@ int exa_register_pde(const char* library_path, int* pde_id);
  * EXA_PDE_FLAG_NCP -- it carries a non-conservative product;
  * EXA_PDE_FLAG_ADMISSIBLE -- it says itself what the a-posteriori limiter's detector checks (exa_lim_snapshot / exa_lim_detect below);
  * EXA_PDE_FLAG_CONSERVATIVE -- its side library carries the limiter's conservative DG / FV interface (exa_lim_face_flux /
- * exa_lim_interface_correct below): pde_codegen.SympyPDE(conservative_interface=True), never together with XT or NCP. */
+ * exa_lim_interface_correct below): pde_codegen.SympyPDE(conservative_interface=True), never together with XT or NCP;
+ * EXA_PDE_FLAG_MUSCL_HANCOCK -- its side library carries the second-order patch update (EXA_FV_MUSCL_HANCOCK):
+ * pde_codegen.SympyPDE(muscl_hancock=True), conservative terms of the state alone (no XT, no NCP, no source). */
 #define EXA_PDE_FLAG_XT 1
 #define EXA_PDE_FLAG_NCP 2
 #define EXA_PDE_FLAG_ADMISSIBLE 4
 #define EXA_PDE_FLAG_CONSERVATIVE 8
+#define EXA_PDE_FLAG_MUSCL_HANCOCK 16
 int exa_pde_flags(int pde);
 
 /* ---- point-wise PDE terms (Functions.h:2-3) ---------------------------------- */
