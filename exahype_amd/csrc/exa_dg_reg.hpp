@@ -43,6 +43,12 @@ template <class PDE> struct DirFlux<PDE, true> {
     typename PDE::Dir c;
     __device__ inline DirFlux(int d, double sc) { PDE::dir_init(c, d, sc); }
     __device__ inline void operator()(const double* q, const double* a, double* F) const { PDE::flux_scaled_dir(q, a, c, F); }
+    __device__ inline double scale() const {                          // the lane's scale, re-formed where it is used: two additions per task against
+        double a = c.psc[0];                                           // two registers held through the step
+        asm volatile("" : "+v"(a));
+        return (a + c.psc[1]) + c.psc[2];
+    }
+    __device__ inline void put(const double* pv, double vn, double sc, double* F) const { PDE::flux_scaled_put(pv, vn, c, sc, F); }
 };
 template <class PDE> struct DirFlux<PDE, false> {
     int d;
@@ -54,6 +60,16 @@ template <class PDE> struct DirFlux<PDE, false> {
         else PDE::template flux_scaled<2>(q, a, sc, F);
     }
 };
+
+// ---- primitives instead of q | flux scalars ---------------------------------------------------------------------------
+// A PDE struct may further provide `NPUT`, `PUT_VN`, `put_fast(q, out)` and `flux_scaled_put(put, vn, dir, sc, F)` (exa_pde.hpp: Euler puts the momenta,
+// 1/rho, E + p and p): the owners put those NPUT values per node and level, a pencil task reads them and, a second time, value PUT_VN + d of its own
+// direction -- the normal component is selected by the ADDRESS of a load, not by arithmetic on the masks.  Term sets without these members keep the image
+// q | aux and the code they had.
+template <class P, class = void> struct pde_has_put : std::false_type {};
+template <class P> struct pde_has_put<P, std::void_t<decltype(P::NPUT), decltype(P::PUT_VN)>> : std::true_type {};
+template <class P, bool HAS = pde_has_put<P>::value> struct pde_nput { static constexpr int value = 0, vn = 0; };
+template <class P> struct pde_nput<P, true> { static constexpr int value = P::NPUT, vn = P::PUT_VN; };
 
 #ifndef EXA_REG_PRIO
 #define EXA_REG_PRIO 1
@@ -96,7 +112,6 @@ template <int N, class PDE, int CPW = 1> struct StageAReg {
     static constexpr bool PAIRED = EXA_REG_PAIRED != 0;
     static constexpr int NVA = NV + NA;
     static constexpr int PS2 = 2 * VS;                                // stride of a pair array
-    static constexpr int SOFF = NVA * VS;                             // S_d at SOFF + d * QSZ
     // ncp term sets: three more arrays G_d = (D q) / h_d behind the sums -- the derive phase contracts q itself along its pencils, the node OWNER
     // evaluates B_d(q) G_d with the state it holds in registers (one cell per workgroup: 128 KB)
     // r5 (EXA_REG_NCP_ALIAS, default): the gradients take the place of the SUMS instead -- a step becomes [gradients] barrier [owners: B_d(q) G_d into
@@ -106,6 +121,10 @@ template <int N, class PDE, int CPW = 1> struct StageAReg {
 #define EXA_REG_NCP_ALIAS 1
 #endif
     static constexpr bool NCPV = pde_has_ncp<PDE>::value;
+    // PUT: the owners put the term set's primitives (pde_has_put above) -- sets of the state alone with a per-lane-normal flux, 8-byte layout
+    static constexpr bool PUT = pde_has_put<PDE>::value && pde_has_dir<PDE>::value && !NCPV && !pde_has_xt<PDE>::value && !PAIRED;
+    static constexpr int NIMG = PUT ? pde_nput<PDE>::value : NVA;     // values per node and level in front of the sums
+    static constexpr int SOFF = NIMG * VS;                            // S_d at SOFF + d * QSZ
     static constexpr bool GALIAS = NCPV && EXA_REG_NCP_ALIAS != 0;
     static constexpr int GOFF = GALIAS ? SOFF : SOFF + 3 * QSZ;
     static constexpr int PIC_D = SOFF + ((NCPV && !GALIAS) ? 6 : 3) * QSZ;
@@ -162,6 +181,8 @@ dg_stage_a_reg_kernel(const double* u_in, double* u_out, double* __restrict__ tr
     constexpr int NN = G::NN, NF = G::NF, SL = G::SL, PX = G::PX, PY = G::PY;
     constexpr int NT = SA::NT, LS = SA::LS, VS = SA::VS, QSZ = SA::QSZ, SOFF = SA::SOFF, FS = SA::FS, NVA = SA::NVA, PS2 = SA::PS2;
     [[maybe_unused]] constexpr int GOFF = SA::GOFF;
+    constexpr bool PUT = SA::PUT;
+    constexpr int NIMG = SA::NIMG, NLD = PUT ? NIMG + 1 : NVA;        // a pencil task's loads per node (PUT: + the normal component)
     constexpr int H = N / 2;
     extern __shared__ __attribute__((aligned(16))) double lds_all[];
     const int half = __builtin_amdgcn_readfirstlane(threadIdx.x >> 8);  // which of the workgroup's cells in flight (wave-uniform)
@@ -222,6 +243,7 @@ dg_stage_a_reg_kernel(const double* u_in, double* u_out, double* __restrict__ tr
     constexpr int NE = H * N + H + 1;
     struct Task {                                                      // one pencil task, decoded: first node, node stride (elements), array group of its sums
         int off, ps, so;
+        int vo;                                                        // (PUT: bytes from a node's first value to its normal component of the task's direction)
         bool on;
         int d, ls;                                                     // (XT / NCP: direction and level slot)
         double xa, xb;                                                 // (XT: reference coordinates xi of the pencil's two fixed node indices, axes ascending)
@@ -233,6 +255,7 @@ dg_stage_a_reg_kernel(const double* u_in, double* u_out, double* __restrict__ tr
         k.off = ls * SL + (d == 0 ? a * PY + b : (d == 1 ? a * PX + b : a * PX + b * PY));
         k.ps = d == 0 ? PX : (d == 1 ? PY : 1);
         k.so = SOFF + d * QSZ;                                         // array group of this direction's sums
+        k.vo = PUT ? (pde_nput<PDE>::vn + d) * VS * (int)sizeof(double) : 0;
         k.d = d;
         k.ls = ls;
         if constexpr (XT) {
@@ -288,12 +311,29 @@ dg_stage_a_reg_kernel(const double* u_in, double* u_out, double* __restrict__ tr
         constexpr int DC = decltype(dc)::value;
         if (tk.on && active_now) {
             const int off = tk.off, ps = tk.ps;
-            double qa[N][NVA];                                         // q | flux scalars of the six nodes
+            double qa[N][NLD];                                         // q | flux scalars of the six nodes (PUT: primitives | normal component)
+            auto ld_node = [&](int jn) {
+                if constexpr (PUT) {
+                    // the address of the normal component is formed behind the node's other loads (the asm keeps its place among the volatile
+                    // loads) and lives only until its load is issued, in the register the value arrives in: the task holds its six node
+                    // addresses through the step, as before, not twelve
+                    const volatile __attribute__((address_space(3))) double* a = &lds[off + jn * ps];
+#pragma unroll
+                    for (int k = 0; k < NIMG; k++) qa[jn][k] = a[k * VS];
+                    const volatile __attribute__((address_space(3))) double* b;
+                    asm volatile("v_add_u32 %0, %1, %2" : "=v"(b) : "v"(a), "v"(tk.vo));
+                    qa[jn][NIMG] = *b;
+                } else {
+                    ld_group(0, off + jn * ps, qa[jn]);
+                }
+            };
 #pragma unroll
             for (int j = 0; j < H; j++) {
-                ld_group(0, off + j * ps, qa[j]);
-                ld_group(0, off + (N - 1 - j) * ps, qa[N - 1 - j]);
+                ld_node(j);
+                ld_node(N - 1 - j);
             }
+            [[maybe_unused]] double scl = 0.0;
+            if constexpr (PUT) scl = fx.scale();
             [[maybe_unused]] const double tl = tk.ls ? tB : tA;
             [[maybe_unused]] const int dd = DC >= 0 ? DC : tk.d;
             [[maybe_unused]] const double scd = dd == 0 ? idx0 : (dd == 1 ? idx1 : idx2);
@@ -311,6 +351,9 @@ dg_stage_a_reg_kernel(const double* u_in, double* u_out, double* __restrict__ tr
                 } else if constexpr (DC >= 0) {
                     PDE::template flux_scaled<DC>(qa[j], qa[j] + NV, scd, Fa);
                     PDE::template flux_scaled<DC>(qa[N - 1 - j], qa[N - 1 - j] + NV, scd, Fb);
+                } else if constexpr (PUT) {
+                    fx.put(qa[j], qa[j][NIMG], scl, Fa);
+                    fx.put(qa[N - 1 - j], qa[N - 1 - j][NIMG], scl, Fb);
                 } else {
                     fx(qa[j], qa[j] + NV, Fa);
                     fx(qa[N - 1 - j], qa[N - 1 - j] + NV, Fb);
@@ -389,7 +432,9 @@ dg_stage_a_reg_kernel(const double* u_in, double* u_out, double* __restrict__ tr
     // arithmetic of the next pair (stored all at the end, the 30 stores of each of the four waves queue up in front of the barrier)
     auto derive_b = [&](const Task& tk, const double (&Em)[NE], const double (&e)[H][NV], const double (&o)[H][NV]) {
         if (tk.on && active_now) {
-            const int off = tk.off, ps = tk.ps, so = tk.so;
+            // (PUT: the six store addresses are formed again in every step -- six integer additions; kept through the step like the load addresses
+            // they are six registers the kernel does not have)
+            const int off = tk.off, ps = tk.ps, so = PUT ? opaque_v(tk.so) : tk.so;
 #pragma unroll
             for (int i = 0; i < H; i++) {
                 // s_i = M + P, s_{N-1-i} = M - P with M = sum_j Eo[j][i] o_j, P = sum_j Ee[j][i] e_j: the P chain starts from M (no separate add),
@@ -567,11 +612,17 @@ dg_stage_a_reg_kernel(const double* u_in, double* u_out, double* __restrict__ tr
 
         // what the pencil tasks read of level slot ls at this owner's node: q and the cached flux scalars
         auto put_level = [&](int ls, const double (&qv)[NV]) {
-            double qa[NVA];
+            if constexpr (PUT) {
+                double pv[NIMG];
+                PDE::put_fast(qv, pv);
+                st_group(0, o_n + ls * SL, pv);
+            } else {
+                double qa[NVA];
 #pragma unroll
-            for (int v = 0; v < NV; v++) qa[v] = qv[v];
-            PDE::aux_fast(qv, qa + NV);
-            st_group(0, o_n + ls * SL, qa);
+                for (int v = 0; v < NV; v++) qa[v] = qv[v];
+                PDE::aux_fast(qv, qa + NV);
+                st_group(0, o_n + ls * SL, qa);
+            }
         };
         // ---- Picard iteration 0: the iterate is constant in time -- one level, row sums of T
 #ifdef EXA_FUSE_ABL_NOPROLOGUE
@@ -719,6 +770,10 @@ dg_stage_a_reg_kernel(const double* u_in, double* u_out, double* __restrict__ tr
             for (int ls = 0; ls < NL; ls++) put_level(ls, qq[l0 + ls]);
         };
         constexpr int IT0 = XT ? 0 : 1;                                // first full iteration
+        // PUT: the task is decoded again for every cell, behind an opaque copy -- about 30 integer instructions per cell, and the masks, strides
+        // and node addresses do not live through the closing phases and the one-kernel step's prologue, where the trace values are in flight
+        // (held over them, the fused kernel spilled 8 registers there)
+        if constexpr (PUT) decode(opaque_v(pk2), tk2, fx2);
         if (n_it > IT0 && owner) load_levels(std::integral_constant<int, 0>{}, q);
         // r5 (EXA_REG_DEFER_FOLD: 0 never, 1 term sets with an ncp or with terms that see x, t (default), 2 every term set): the time contraction of an iteration DEFERRED to its end, as in
         // exa_dg_m8.hpp -- a fold only keeps S_x + S_y + S_z (+ source / ncp terms) of its two levels; the owner state in front of the derive phases is
@@ -947,7 +1002,10 @@ dg_stage_a_reg_kernel(const double* u_in, double* u_out, double* __restrict__ tr
             sload<N>(ops_here<N>(ops_raw)->phiL, pl);
             sload<N>(ops_here<N>(ops_raw)->phiR, pr);
             static_assert(NV * NF <= NT, "closing phases: one round per direction");
-            const int v = tid / NF, t = tid - v * NF;
+            // (PUT: the lane's (v, t) from an opaque copy -- computed at the top of the cell, the trace offset they give lived through the Picard
+            // loop and was spilled by the fused kernel)
+            const int tv = PUT ? opaque_v(tid) : tid;
+            const int v = tv / NF, t = tv - v * NF;
             static_for<0, DIM>([&](auto dc) {
                 constexpr int D = decltype(dc)::value;
                 if (tid < NV * NF) {

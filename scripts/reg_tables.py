@@ -8,13 +8,20 @@ This script searches the strides (PY, PX, SL) that fit two workgroups into the 1
 it reports the extra LDS cycles per step and prints the tables as C initialisers.  The C++ side (dg_inst.hip fill_reg_tables) holds a
 deterministic constructive version of the same model; this script is what showed which layout it has to aim at.
 
-usage: reg_tables.py [N] [iters]
+The primitive image (exa_dg_reg.hpp StageAReg::PUT: the owners put NPUT = 6 values per node, a pencil task reads them and, a second time, the
+normal component from slot PUT_VN + d of ITS direction) adds one read per node whose slot differs between the lanes of a group that mixes
+directions: `library_table` restates the constructive tables of dg_inst.hip fill_reg_tables (8-byte layout), `step_cost` prices a two-level
+step of a table under either image, the second read included.
+
+usage: reg_tables.py [N] [iters]        the search
+       reg_tables.py model              modelled conflict cycles per step of the shipped table, both images
 """
 import random
 import sys
 
-N = int(sys.argv[1]) if len(sys.argv) > 1 else 6
-ITERS = int(sys.argv[2]) if len(sys.argv) > 2 else 200000
+ARGS = sys.argv[1:] if __name__ == "__main__" else []        # (imported -- tests/test_reg_tables_model.py: the defaults)
+N = int(ARGS[0]) if len(ARGS) > 0 and ARGS[0].isdigit() else 6
+ITERS = int(ARGS[1]) if len(ARGS) > 1 else 200000
 NV, NA, LG = 5, 2, 2
 NF, NN = N * N, N * N * N
 LDS_DOUBLES = (160 * 1024 // 2 - 512) // 8         # per workgroup, two per CU, a little slack for static arrays
@@ -57,6 +64,104 @@ def derive_cost(assign, PY, PX, SL, detail=False):
             rd += (NV + NA) * max(0, group_cost(ra, 32, 32) - 2)
             wr += NV * max(0, group_cost(wa, 16, 16) - 6)
     return (rd, wr) if detail else rd + wr
+
+
+NPUT, PUT_VN = 6, 0                                # exa_pde.hpp Euler: m_x, m_y, m_z, 1/rho, E + p, p; normal momentum of direction d in slot PUT_VN + d
+
+
+def library_geometry():
+    """strides of exa_dg_reg.hpp RegGeo<N>: unpadded rows and planes, odd level stride"""
+    return N, N * N, NN + (1 if NN % 2 == 0 else 0)
+
+
+def library_table(nl=2):
+    """lane -> (d, ls, t) or None: dg_inst.hip fill_reg_tables restated (8-byte layout), nl levels in the step"""
+    PY, PX, SL = library_geometry()
+    _, pbase, _ = geometry(PY, PX, SL)
+    ps = (PX, PY, 1)
+    QSZ, NT, NG = NV * LG * SL, 256, 8
+
+    def base(k):
+        return k[1] * SL + pbase(k[0], k[2])
+    out = [None] * NT
+    groups = []
+    for d in range(3):
+        byres = [[] for _ in range(32)]
+        for ls in range(nl):
+            for t in range(NF):
+                byres[base((d, ls, t)) & 31].append((d, ls, t))
+        g = 0
+        while True:
+            grp = [b[g] for b in byres if len(b) > g]
+            if not grp:
+                break
+            groups.append(grp)
+            g += 1
+    groups.sort(key=lambda grp: -len(grp))             # (stable, as std::stable_sort)
+    npure = min(len(groups), NG)
+    while npure > 0 and sum(len(g) for g in groups[npure:]) > 32 * (NG - npure):
+        npure -= 1
+    for g in range(npure):
+        for k in groups[g]:
+            out[32 * g + (base(k) & 31)] = k
+
+    def group_score(g):
+        score = 0
+        for jj in range(N):
+            seen_r, seen_w = {}, {}
+            for lane in range(32):
+                k = out[32 * g + lane]
+                if k is None:
+                    continue
+                a = base(k) + jj * ps[k[0]]
+                w = a + k[0] * QSZ
+                seen_r.setdefault(a & 31, set()).add(a)
+                seen_w.setdefault((lane // 16, w & 15), set()).add(w)
+            mr = max([1] + [len(v) for v in seen_r.values()])
+            mw = [max([1] + [len(v) for (h, _), v in seen_w.items() if h == half]) for half in range(2)]
+            score += 2 * (NV + NA) * (mr - 1) + NV * (mw[0] - 1 + mw[1] - 1)
+        return score
+    for grp in groups[npure:]:
+        for k in grp:
+            best_lane, best = -1, 1 << 30
+            for lane in range(32 * npure, NT):
+                if out[lane] is not None:
+                    continue
+                before = group_score(lane // 32)
+                out[lane] = k
+                delta = group_score(lane // 32) - before
+                out[lane] = None
+                if delta < best:
+                    best, best_lane = delta, lane
+            out[best_lane] = k
+    return out
+
+
+def step_cost(assign, put):
+    """Modelled extra LDS cycles of the derive phase of one two-level step of the library's geometry (the measure of derive_cost), as a dict:
+    `same` = the reads every lane makes at the same slot (7 per node for the image q | 1/rho | p, NPUT for the primitive image), `vn` = the second
+    read of the normal component (primitive image only: slot PUT_VN + d, i.e. a bank shift of (PUT_VN + d) * LG * SL doubles per direction),
+    `wr` = the stores of the sums (their arrays lie QSZ apart whatever the image: a common shift changes no conflict)."""
+    PY, PX, SL = library_geometry()
+    ps, pbase, _ = geometry(PY, PX, SL)
+    VS, QSZ = LG * SL, NV * LG * SL
+    same = vn = wr = 0
+    for w in range(4):
+        lanes = assign[64 * w:64 * w + 64]
+        for jj in range(N):
+            ra = [None if t is None else t[1] * SL + pbase(t[0], t[2]) + jj * ps[t[0]] for t in lanes]
+            va = [None if t is None else a + (PUT_VN + t[0]) * VS for t, a in zip(lanes, ra)]
+            wa = [None if t is None else a + t[0] * QSZ for t, a in zip(lanes, ra)]
+            same += (NPUT if put else NV + NA) * max(0, group_cost(ra, 32, 32) - 2)
+            if put:
+                vn += max(0, group_cost(va, 32, 32) - 2)
+            wr += NV * max(0, group_cost(wa, 16, 16) - 6)
+    return dict(same=same, vn=vn, wr=wr, total=same + vn + wr)
+
+
+def mixed_groups(assign):
+    """the 32-lane groups of a table that hold pencils of more than one direction"""
+    return [g for g in range(len(assign) // 32) if len({t[0] for t in assign[32 * g:32 * g + 32] if t is not None}) > 1]
 
 
 def owner_cost(order, PY, PX, SL):
@@ -117,6 +222,13 @@ def owner_order(PY, PX, SL):
     return order[:256] if len(order) >= 256 else order
 
 
+if __name__ == "__main__" and ARGS[:1] == ["model"]:
+    tab = library_table(2)
+    old, new = step_cost(tab, False), step_cost(tab, True)
+    print("shipped table, two-level step: groups that mix directions %s" % mixed_groups(tab))
+    print("image q | 1/rho | p : modelled extra LDS cycles per step %s" % old)
+    print("primitive image     : modelled extra LDS cycles per step %s" % new)
+    sys.exit(0)
 if __name__ == "__main__":
     cands = []
     for PY in (N, N + 1):
