@@ -160,13 +160,10 @@ __device__ unsigned long long g_exa_wg_span[2 * 1024];     // per workgroup: sta
 #else
 #define EXA_ABL_COND_SKIP_D
 #endif
-// Stage B: the eigenvalues of the trace states by the IEEE sequences (default) or by the fast reciprocal / square root.  Measured r4 (same box, two
+// Stage B takes the eigenvalues of the trace states by the IEEE sequences.  The fast reciprocal / square root, measured r4 (same box, two
 // rounds, scripts/quick_bench_stage_b.py): 128^3 p = 5 15.70 / 15.85 ms IEEE against 16.52 / 16.50 fast (the dense variant LOSES 4 %: the kernel is
 // bound by its memory latency chain, and the shorter arithmetic changes nothing but the schedule), 64^3 p = 7 4.07 / 4.10 against 3.98 / 4.05, 128^3 p = 3
 // 5.96 / 6.09 against 6.05 / 6.04 -- not adopted.
-#ifndef EXA_STAGE_B_FAST_EIG
-#define EXA_STAGE_B_FAST_EIG 0
-#endif
 #ifdef EXA_ABL_NOFMA
 #define EXA_FMA(acc, a, b) asm volatile("" : "+v"(acc) : "v"(a), "v"(b))
 #else
@@ -283,13 +280,7 @@ template <int DIM, int N, class PDE, int CPB> struct StageA {
     //   1 "early": every pencil loaded, barrier (R), sums stored at once, barrier (1), time update
     // (a third form -- the x group waits for a count of the y / z waves whose loads are done instead of for a barrier -- timed
     //  like 0 at N = 6 and 2 % better than 1 at N = 5; not kept: see the profile note and commit a7e35b6)
-#if defined(EXA_A_EARLY_STORE)
-    static constexpr int MODE = 1;
-#elif defined(EXA_A_LATE_STORE)
-    static constexpr int MODE = 0;
-#else
     static constexpr int MODE = (DIM == 3 && (N == 5 || N == 3)) ? 1 : 0;
-#endif
 };
 
 // Cell image in LDS: three q-sized arrays Q | A | B, each SoA [var][time slab][node].
@@ -508,17 +499,11 @@ dg_stage_a_kernel(const double* __restrict__ u_in, double* __restrict__ u_out, d
                 const int off = c * CS + l * SL + G::pbase(D, t);
                 // even-odd form of the centro-antisymmetric D (DgOps::DEO): half the FMAs --
                 // s_i -+ s_{N-1-i} from F_j +- F_{N-1-j}; odd N: the middle node and the middle row on top.
-                // (tried in round 2, measured and left as opt-in macros: the whole operator in SGPRs first -- one batch, one
-                // wait -- and every LDS load of the pencil issued before the first flux; both lose to the form below, whose
-                // waits hide behind the other two waves of the SIMD)
+                // (tried in round 2 and measured, profiles/r02_stage_a_variants.txt: the whole operator in SGPRs first -- one batch, one
+                // wait, 2.5 % slower at N = 6 -- and every LDS load of the pencil issued before the first flux, 0.5 % slower; both lose to
+                // the form below, whose waits hide behind the other two waves of the SIMD)
                 constexpr int H = N / 2;
-                constexpr int NE = H * N + H + 1;
-#ifndef EXA_A_SLOAD_D
                 const EXA_AS4 double* Em = ops_here<N>(ops_raw)->DEO;
-#else                // measured 2.5 % slower at N = 6 (profiles/r02_stage_a_variants.txt): 44 more live SGPRs, the waits were hidden
-                double Em[NE];
-                sload<NE>(ops_here<N>(ops_raw)->DEO, Em);
-#endif
                 // pencils along the contiguous axis (ps == 1, N even): 16-byte LDS accesses -- the pencil
                 // bases are 3*t 16-byte units apart, a permutation mod 16 for every hardware lane group, so
                 // ds_read_b128 / ds_write_b128 are conflict-free where 8-byte accesses are 2-way conflicted
@@ -533,17 +518,6 @@ dg_stage_a_kernel(const double* __restrict__ u_in, double* __restrict__ u_out, d
                             qw[2 * jj][v] = t2.x;
                             qw[2 * jj + 1][v] = t2.y;
                         }
-                } else {
-#ifdef EXA_A_LOADS_FIRST   // (every load of the pencil first: 0.5 % slower at N = 6, more live registers)
-                    // in the order the even-odd form consumes them: node j, its mirror, next j
-#pragma unroll
-                    for (int j = 0; j < (N + 1) / 2; j++)
-#pragma unroll
-                        for (int v = 0; v < NV; v++) {
-                            qw[j][v] = EXA_LD(off + v * NTS * SL + j * ps);
-                            if (j != N - 1 - j) qw[N - 1 - j][v] = EXA_LD(off + v * NTS * SL + (N - 1 - j) * ps);
-                        }
-#endif
                 }
                 {
                     double P[H > 0 ? H : 1][NV], M[H > 0 ? H : 1][NV], mid[NV];
@@ -557,7 +531,6 @@ dg_stage_a_kernel(const double* __restrict__ u_in, double* __restrict__ u_out, d
                     for (int j = 0; j < H; j++) {
                         const int jm = N - 1 - j;                // mirror node
                         double aa[nz(NA)], ab[nz(NA)], Fa[NV], Fb[NV];
-#ifndef EXA_A_LOADS_FIRST
                         if constexpr (!WIDE) {
 #pragma unroll
                             for (int v = 0; v < NV; v++) {
@@ -565,7 +538,6 @@ dg_stage_a_kernel(const double* __restrict__ u_in, double* __restrict__ u_out, d
                                 qw[jm][v] = EXA_LD(off + v * NTS * SL + jm * ps);
                             }
                         }
-#endif
                         PDE::aux_fast(qw[j], aa);
                         PDE::template flux_scaled<D>(qw[j], aa, idx[D], Fa);
                         PDE::aux_fast(qw[jm], ab);
@@ -593,12 +565,10 @@ dg_stage_a_kernel(const double* __restrict__ u_in, double* __restrict__ u_out, d
                     }
                     if constexpr (N % 2 == 1) {                  // middle node
                         double aa[nz(NA)], Fa[NV];
-#ifndef EXA_A_LOADS_FIRST
                         if constexpr (!WIDE) {
 #pragma unroll
                             for (int v = 0; v < NV; v++) qw[H][v] = EXA_LD(off + v * NTS * SL + H * ps);
                         }
-#endif
                         PDE::aux_fast(qw[H], aa);
                         PDE::template flux_scaled<D>(qw[H], aa, idx[D], Fa);
 #pragma unroll
@@ -1255,11 +1225,7 @@ dg_stage_b_kernel(double* __restrict__ u, const double* __restrict__ trace, Stag
                 Fm[v] = pm[(NV + v) * NF + y];
                 Fp[v] = pp[(NV + v) * NF + y];
             }
-#if EXA_STAGE_B_FAST_EIG
-            lam = fmax(PDE::maxeig_fast(qm, d), PDE::maxeig_fast(qp, d));
-#else
             lam = fmax(PDE::maxeig(qm, d), PDE::maxeig(qp, d));
-#endif
         }
         // face-wide maximum: segmented butterfly over the GS lanes of the face (inactive lanes carry 0)
 #pragma unroll
@@ -1397,11 +1363,7 @@ dg_stage_b_dense_kernel(double* __restrict__ u, const double* __restrict__ trace
                 face_node_coords<DIM, N>(geo, cc, d, face, y, xf);
                 lam[task] = fmax(PDE::maxeig_xt(qm[k], xf, geo.t + 0.5 * dt, d), PDE::maxeig_xt(qp[k], xf, geo.t + 0.5 * dt, d));
             } else {
-#if EXA_STAGE_B_FAST_EIG
-                lam[task] = fmax(PDE::maxeig_fast(qm[k], d), PDE::maxeig_fast(qp[k], d));
-#else
                 lam[task] = fmax(PDE::maxeig(qm[k], d), PDE::maxeig(qp[k], d));
-#endif
             }
         }
     }

@@ -141,12 +141,9 @@ dg_stage_a_m8_kernel(const double* __restrict__ u_in, double* __restrict__ u_out
     const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
     [[maybe_unused]] const int bt = lane, grp = wave & 3;             // (stamp builds)
     EXA_STAMP_INIT();
-#ifndef EXA_M8_STAGGER
-#define EXA_M8_STAGGER 1
-#endif
     // the two waves of a SIMD (wave and wave + 4) at different static issue priorities: the favoured one runs ahead inside a phase, so that its
     // LDS traffic falls beside the other's arithmetic (12.23 -> 12.13 ms per 32^3 launch; level 1 or 3: the same)
-    if (EXA_M8_STAGGER > 0 && wave >= 4) __builtin_amdgcn_s_setprio(EXA_M8_STAGGER);
+    if (wave >= 4) __builtin_amdgcn_s_setprio(1);
 
     // owner slot -> node permutation that makes the node-linear LDS phases conflict-free under the padded strides (exa_dg_stream.hpp)
     int o_n;
@@ -361,88 +358,11 @@ dg_stage_a_m8_kernel(const double* __restrict__ u_in, double* __restrict__ u_out
 #ifndef EXA_M8_XEARLY        // 1: the in-place round's operands requested in front of the barrier (r5).  Measured: 89.6 against 88.3 ms per 64^3 launch (no more
 #define EXA_M8_XEARLY 0      // registers, no spill -- the loads merely compete with the stores of the rounds in front of the barrier): off.
 #endif
-#ifndef EXA_M8_PIPE          // (measured SLOWER: 117.3 against 98.2 ms per 64^3 launch -- the 28 VGPRs of the next round's operands do not exist: 204 B of scratch)
-#define EXA_M8_PIPE 0
-#endif
     using M0 = std::integral_constant<int, 0>;
     using M1 = std::integral_constant<int, 1>;
     auto derive = [&](int tb, double tA, double tB, auto mode) {      // tb: 0 = steps of two levels, 1 = iteration 0 (one level)
         double hx[2][NV];
-#ifdef EXA_M8_SKEW            // (experiment: the second wave of every SIMD starts its rounds EXA_M8_SKEW x 64 cycles late, so that its LDS phases fall beside the other's arithmetic)
-        if (wave >= 4) __builtin_amdgcn_s_sleep(EXA_M8_SKEW);
-#endif
-#if EXA_M8_PIPE
-        static_assert(!XT && !NCP && !EXA_M8_LAYOUT, "EXA_M8_PIPE: built-in term sets, r3 layout only");
-        // software-pipelined over the three rounds: the LDS loads of the next round are issued in front of the matrix instructions and the
-        // stores of the current one (they read Q and the scalars, which no round writes), so their latency and the store queue overlap
-        const int t_ = opaque_v(tid), dj = opaque_v(d_j);
-        struct Ops { double qa[NV], qb[NV], aa[nz(NA)], ab[nz(NA)]; };
-        auto offs = [&](auto dc, int& na, int& nb) -> bool {
-            constexpr int D = decltype(dc)::value;
-            const int off = ltab[(tb * 3 + D) * NT + t_];
-            const bool have = off != 0xffff;                          // (wave-uniform: a wave has 16 pencils or none)
-            const int o2 = have ? off : 0;
-            na = o2 + dj * G::pstride(D);
-            nb = o2 + (N - 1 - dj) * G::pstride(D);
-            return have;
-        };
-        auto load = [&](int na, int nb, Ops& r) {
-#pragma unroll
-            for (int v = 0; v < NV; v++) {
-                r.qa[v] = EXA_SLD(na + v * VS);
-                r.qb[v] = EXA_SLD(nb + v * VS);
-            }
-#pragma unroll
-            for (int k = 0; k < NA; k++) {
-                r.aa[k] = EXA_SLD(AXO + na + k * VS);
-                r.ab[k] = EXA_SLD(AXO + nb + k * VS);
-            }
-        };
-        auto evenodd = [&](auto dc, const Ops& r, double (&e)[NV], double (&o)[NV]) {
-            constexpr int D = decltype(dc)::value;
-            double Fa[NV], Fb[NV];
-            const double sc = D == 0 ? idx0 : (D == 1 ? idx1 : idx2);
-            PDE::template flux_scaled<D>(r.qa, r.aa, sc, Fa);
-            PDE::template flux_scaled<D>(r.qb, r.ab, sc, Fb);
-#pragma unroll
-            for (int v = 0; v < NV; v++) {
-                e[v] = Fa[v] + Fb[v];
-                o[v] = Fa[v] - Fb[v];
-            }
-        };
-        auto matrix = [&](auto dc, bool have, int na, int nb, const double (&e)[NV], const double (&o)[NV]) {
-            constexpr int D = decltype(dc)::value;
-#pragma unroll
-            for (int v = 0; v < NV; v++) {
-                const double Pv = __builtin_amdgcn_mfma_f64_4x4x4f64(aEe, e[v], 0.0, 0, 0, 0);
-                const double Mv = __builtin_amdgcn_mfma_f64_4x4x4f64(aEo, o[v], 0.0, 0, 0, 0);
-                if constexpr (D == 0) {
-                    hx[0][v] = Mv + Pv;
-                    hx[1][v] = Mv - Pv;
-                } else if (have) {
-                    lds[D * QSZ + na + v * VS] = Mv + Pv;
-                    lds[D * QSZ + nb + v * VS] = Mv - Pv;
-                }
-            }
-        };
-        using D0 = std::integral_constant<int, 0>;
-        using D1 = std::integral_constant<int, 1>;
-        using D2 = std::integral_constant<int, 2>;
-        int na1, nb1, na2, nb2, na0, nb0;
-        const bool h1 = offs(D1{}, na1, nb1), h2 = offs(D2{}, na2, nb2), h0 = offs(D0{}, na0, nb0);
-        (void)h0;
-        Ops r;
-        double e[NV], o[NV];
-        load(na1, nb1, r);
-        evenodd(D1{}, r, e, o);
-        load(na2, nb2, r);                                            // (round z's operands: in flight under round y's matrix instructions and stores)
-        matrix(D1{}, h1, na1, nb1, e, o);
-        evenodd(D2{}, r, e, o);
-        load(na0, nb0, r);
-        matrix(D2{}, h2, na2, nb2, e, o);
-        evenodd(D0{}, r, e, o);
-        matrix(D0{}, true, 0, 0, e, o);                               // x last: its sums wait in registers for the barrier
-#elif EXA_M8_XINPLACE
+#if EXA_M8_XINPLACE
         // r5: the x round runs BEHIND the barrier that ends the y and z rounds and stores its sums straight over Q -- the four lanes of an x pencil (one wave) are
         // the only readers of the nodes they overwrite, and they have read them (in-order LDS) before their matrix instructions complete.  The separate
         // "Q := S_x" phase (10 stores per lane with nothing beside them, 955 of the 7 800 cycles of a step in the stamp build) and the ten values held over the
@@ -523,17 +443,6 @@ dg_stage_a_m8_kernel(const double* __restrict__ u_in, double* __restrict__ u_out
         for (int k = 0; k < NA; k++) lds[AXO + o_off + ls * SL + k * VS] = a[k];
     };
 
-#ifndef EXA_M8_PREFETCH_U    // 1: the next cell's u requested behind the time averages of this one (in flight under the volume / trace / u* phases).
-#define EXA_M8_PREFETCH_U 0  // Measured r5: 89.5 against 88.4 ms per 64^3 launch -- the ten registers it holds cost 4 spilled VGPRs; off.
-#endif
-    [[maybe_unused]] double un[NV];
-    if constexpr (EXA_M8_PREFETCH_U) {
-        if ((long)blockIdx.x < box.nbox) {
-            const double* p0 = u_in + (box.cell(blockIdx.x) * NN + o_n) * NV;
-#pragma unroll
-            for (int v = 0; v < NV; v++) un[v] = p0[v];
-        }
-    }
     for (long b = blockIdx.x; b < box.nbox; b += gridDim.x) {
         const long cell = box.cell(b);
         if constexpr (XT) {
@@ -545,7 +454,7 @@ dg_stage_a_m8_kernel(const double* __restrict__ u_in, double* __restrict__ u_out
         const double* up = u_in + (cell * NN + o_n) * NV;             // (u is re-read where needed: an L2 hit against 10 VGPRs of a kernel at its cap)
         double u[NV], q[N][NV];
 #pragma unroll
-        for (int v = 0; v < NV; v++) u[v] = EXA_M8_PREFETCH_U ? un[v] : up[v];
+        for (int v = 0; v < NV; v++) u[v] = up[v];
 
         // (XT: the terms depend on the level time -- every iteration is a full one, started from q_l = u)
         if constexpr (XT) {
@@ -590,10 +499,6 @@ dg_stage_a_m8_kernel(const double* __restrict__ u_in, double* __restrict__ u_out
         };
         constexpr int IT0 = XT ? 0 : 1;                                // first full iteration
         if (n_it > IT0) load_levels(std::integral_constant<int, 0>{}, q);
-#ifndef EXA_M8_DEFER
-#define EXA_M8_DEFER 1
-#endif
-#if EXA_M8_DEFER
         // r5: the time contraction of an iteration is DEFERRED to its end.  A step only sums S_x + S_y + S_z of its two levels into registers; the
         // FMAs acc[l'] = u - dt sum_l T[l'][l] S_l run once all levels are there (same order in l as before: bit-identical).  Live through the derive
         // rounds of step st: the levels of q not yet in LDS (10 (3 - st) doubles) + the sums so far (10 st) = 30 doubles instead of up to 60 (iterate
@@ -644,69 +549,6 @@ dg_stage_a_m8_kernel(const double* __restrict__ u_in, double* __restrict__ u_out
             if (it + 1 < n_it) load_levels(std::integral_constant<int, 0>{}, q);
             EXA_STAMP(4);
         }
-#else
-        for (int it = IT0; it < n_it; it++) {
-            double acc[N][NV];
-            static_for<0, LS>([&](auto sc_) {
-                constexpr int st = decltype(sc_)::value;
-                constexpr int l0 = 2 * st;
-                EXA_STAMP(4);
-                EXA_M8_SYNC_PUTS();
-                EXA_STAMP(5);
-#ifdef EXA_M8_EARLY_U
-                [[maybe_unused]] double uu[NV];
-                if constexpr (st == 0) {
-#pragma unroll
-                    for (int v = 0; v < NV; v++) uu[v] = up[v];
-                }
-#endif
-                derive(0, XT ? level_t(l0) : 0.0, XT ? level_t(l0 + 1) : 0.0, M0{});
-                EXA_STAMP(6);
-                double Tm[2 * N];                                      // -dt T[l'][l0 + ls], l' fastest
-                sload<2 * N>(step_here<N>(step_raw)->TdtT + l0 * N, Tm);
-#ifndef EXA_M8_EARLY_U
-                [[maybe_unused]] double uu[NV];
-                if constexpr (st == 0) {
-#pragma unroll
-                    for (int v = 0; v < NV; v++) uu[v] = up[v];
-                }
-#endif
-                double Sx[2][NV];                                      // (summed as they arrive: 160 VGPRs of iterate + accumulators leave no room for 30 loads in flight)
-#pragma unroll
-                for (int ls = 0; ls < 2; ls++)
-#pragma unroll
-                    for (int v = 0; v < NV; v++) Sx[ls][v] = sums_at(ls, v);
-                if constexpr (pde_has_source<PDE>::value) {           // q_t + div F = S(q): on the iterate in the owner's registers
-#pragma unroll
-                    for (int ls = 0; ls < 2; ls++) {
-                        double Sq[NV];
-                        source_at(q[l0 + ls], l0 + ls, Sq);
-#pragma unroll
-                        for (int v = 0; v < NV; v++) Sx[ls][v] -= Sq[v];
-                    }
-                }
-                if constexpr (st + 1 < LS) load_levels(std::integral_constant<int, l0 + 2>{}, q);
-#pragma unroll
-                for (int ls = 0; ls < 2; ls++)
-#pragma unroll
-                    for (int lp = 0; lp < N; lp++)
-#pragma unroll
-                        for (int v = 0; v < NV; v++) {
-                            if constexpr (st == 0) acc[lp][v] = fma(Tm[ls * N + lp], Sx[ls][v], ls == 0 ? uu[v] : acc[lp][v]);
-                            else acc[lp][v] = fma(Tm[ls * N + lp], Sx[ls][v], acc[lp][v]);
-                        }
-                if constexpr (st + 1 == LS) {
-                    if (it + 1 < n_it) load_levels(std::integral_constant<int, 0>{}, acc);
-                }
-                EXA_STAMP(7);
-            });
-#pragma unroll
-            for (int l = 0; l < N; l++)
-#pragma unroll
-                for (int v = 0; v < NV; v++) q[l][v] = acc[l][v];
-        }
-
-#endif
 
         // ---- NCP: the time-averaged non-conservative term of the FINAL iterate enters u* point-wise: one more pass of the derive rounds over the
         // levels, non-conservative part only, weighted with w_l by the owners
@@ -780,13 +622,6 @@ dg_stage_a_m8_kernel(const double* __restrict__ u_in, double* __restrict__ u_out
             }
         }
         EXA_STAMP(8);
-        if constexpr (EXA_M8_PREFETCH_U) {
-            if (b + gridDim.x < box.nbox) {
-                const double* pn = u_in + (box.cell(b + gridDim.x) * NN + opaque_v(o_n)) * NV;
-#pragma unroll
-                for (int v = 0; v < NV; v++) un[v] = pn[v];
-            }
-        }
         __syncthreads();
 
         // ---- volume integral (in place over Fbar_d) + face extrapolation: pencil tasks (d, v, t), t fastest

@@ -71,13 +71,9 @@ template <class P> struct pde_has_put<P, std::void_t<decltype(P::NPUT), decltype
 template <class P, bool HAS = pde_has_put<P>::value> struct pde_nput { static constexpr int value = 0, vn = 0; };
 template <class P> struct pde_nput<P, true> { static constexpr int value = P::NPUT, vn = P::PUT_VN; };
 
-#ifndef EXA_REG_PRIO
-#define EXA_REG_PRIO 1
-#endif
 #ifndef EXA_REG_CPW
 #define EXA_REG_CPW 2                          // cells in flight per workgroup: 2 = one 512-thread workgroup per CU, halves one barrier apart (128^3 cells:
 #endif                                         // 154.5 ms; 1 = two 256-thread workgroups: 158.9 ms)
-#define EXA_REG_CPW_DEFAULT EXA_REG_CPW
 
 template <int N> struct RegGeo {
     static constexpr int NN = N * N * N, NF = N * N;
@@ -101,55 +97,31 @@ template <int N, class PDE, int CPW = 1> struct StageAReg {
     static constexpr int LS = (N + LG - 1) / LG;                      // steps per Picard iteration
     static constexpr int VS = LG * G::SL;                             // slot stride
     static constexpr int QSZ = NV * VS;                               // q (and each of the three sum arrays)
-    // PAIRED (-DEXA_REG_PAIRED=1): the values of a node and level lie as 16-byte pairs (+ one 8-byte value where their number is odd), so a
-    // pencil task reads the 7 values of a node with 3 ds_read_b128 + 1 ds_read_b64 instead of 7 ds_read_b64 and writes its 5 sums with
-    // 2 + 1 stores; likewise the owners: 68 LDS instructions per step instead of 116, the same bytes.  Measured SLOWER (21.5 against
-    // 19.4 ms per 64^3 launch, profiles/r03_reg_kernel.txt): SQ_INSTS_LDS -40 %, but SQ_WAIT_INST_LDS +24 % -- a 13-cycle ds_write_b128
-    // holds the wave at the LDS queue longer than two 6-cycle stores interleaved with its arithmetic.  Off by default.
-#ifndef EXA_REG_PAIRED
-#define EXA_REG_PAIRED 0
-#endif
-    static constexpr bool PAIRED = EXA_REG_PAIRED != 0;
     static constexpr int NVA = NV + NA;
-    static constexpr int PS2 = 2 * VS;                                // stride of a pair array
     // ncp term sets: three more arrays G_d = (D q) / h_d behind the sums -- the derive phase contracts q itself along its pencils, the node OWNER
     // evaluates B_d(q) G_d with the state it holds in registers (one cell per workgroup: 128 KB)
-    // r5 (EXA_REG_NCP_ALIAS, default): the gradients take the place of the SUMS instead -- a step becomes [gradients] barrier [owners: B_d(q) G_d into
+    // r5: the gradients take the place of the SUMS instead -- a step becomes [gradients] barrier [owners: B_d(q) G_d into
     // registers] barrier [flux sums] barrier [fold]; two more barriers per step, but the cell image is the 76 KB of a term set without ncp again, and two
     // cells are in flight per CU as everywhere else (one cell per CU = one wave per SIMD was the 2 x of profiles/r04_xt_ncp_kernels.txt)
-#ifndef EXA_REG_NCP_ALIAS
-#define EXA_REG_NCP_ALIAS 1
-#endif
     static constexpr bool NCPV = pde_has_ncp<PDE>::value;
     // PUT: the owners put the term set's primitives (pde_has_put above) -- sets of the state alone with a per-lane-normal flux, 8-byte layout
-    static constexpr bool PUT = pde_has_put<PDE>::value && pde_has_dir<PDE>::value && !NCPV && !pde_has_xt<PDE>::value && !PAIRED;
+    static constexpr bool PUT = pde_has_put<PDE>::value && pde_has_dir<PDE>::value && !NCPV && !pde_has_xt<PDE>::value;
     static constexpr int NIMG = PUT ? pde_nput<PDE>::value : NVA;     // values per node and level in front of the sums
     static constexpr int SOFF = NIMG * VS;                            // S_d at SOFF + d * QSZ
-    static constexpr bool GALIAS = NCPV && EXA_REG_NCP_ALIAS != 0;
-    static constexpr int GOFF = GALIAS ? SOFF : SOFF + 3 * QSZ;
-    static constexpr int PIC_D = SOFF + ((NCPV && !GALIAS) ? 6 : 3) * QSZ;
+    static constexpr int GOFF = SOFF;                                 // (ncp: the gradients G_d, in the arrays of the sums)
+    static constexpr int PIC_D = SOFF + 3 * QSZ;
     static constexpr int FS = G::NN;                                  // closing phases: [array][var][node], arrays qbar | Fbar_x | Fbar_y | Fbar_z (| source)
     static constexpr int FIN_D = (pde_has_source<PDE>::value ? 5 : 4) * NV * FS;
     static constexpr int CELL_D = PIC_D > FIN_D ? PIC_D : FIN_D;      // doubles of LDS per cell in flight
     static constexpr size_t LDS_BYTES = sizeof(double) * ((size_t)CELL_D * CPW + 2 * 3 * N);   // + the one-kernel step's corrector weights
-    static constexpr bool FITS = G::NN <= NT && ((NCPV && !GALIAS) ? 1 : 2) * sizeof(double) * (size_t)CELL_D + 2048 <= 160 * 1024;
+    static constexpr bool FITS = G::NN <= NT && 2 * sizeof(double) * (size_t)CELL_D + 2048 <= 160 * 1024;
     // behind the image of dg_stage_a_kernel (StageA<3, N, PDE, CPB>::IMAGE_BYTES): lane -> packed derive task of a two-level
     // step, and of iteration 0 (one level); packed = d | level slot << 2 | pencil << 3, -1 = idle
     static constexpr int TAB_INTS = 2 * NT;
 };
 
-// Workgroup barrier.  -DEXA_REG_LDS_BARRIER: for LDS data only -- waits for this wave's LDS operations, not for its global loads / stores
-// (the kernel hands nothing through global memory between its lanes, and __syncthreads() makes every wave wait for the acknowledgement
-// of its trace stores).
-__device__ inline void lds_barrier() {
-#ifndef EXA_REG_LDS_BARRIER          // (measured: no difference, 19.5 against 19.4 ms per 64^3 launch -- the plain barrier stays)
-    __syncthreads();
-#else
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup", "local");
-    __builtin_amdgcn_s_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup", "local");
-#endif
-}
+// Workgroup barrier of the kernel outside the one-kernel step (an LDS-only barrier measured no different: 19.5 against 19.4 ms per 64^3 launch)
+__device__ inline void lds_barrier() { __syncthreads(); }
 
 // FUSE (the step as ONE kernel, "stage B folded into stage A"): the cell first finishes the PREVIOUS step -- Rusanov flux on its six
 // faces from the traces that step left (own + neighbours', ghosts where the block ends; face-wide maximum eigenvalue as
@@ -158,13 +130,11 @@ __device__ inline void lds_barrier() {
 // face node (216 face nodes = 216 lanes) are requested during the previous cell's closing phases and stay in flight across its barriers
 // (which wait for LDS operations only in this variant).  Sequence of a run: A, [B o A] x (n - 1), B.
 
-// Term sets with a non-conservative product run ONE cell per workgroup at one wave per SIMD (REG_CPW_OF = 1, second launch bound 1): their three
-// gradient arrays G_d = (D q) / h_d sit in LDS behind the sums (StageAReg::GOFF; 128 KB per cell), the node owners evaluate B_d(q) G_d.
-// (First form: B_d(q_i) (D q)_i evaluated along the pencil in the derive phase -- six states at once on top of the owner state, ~290 VGPRs,
-// 25 - 30 ms per 32^3 launch of Euler-with-pressure-as-ncp against 26.3 of the plain kernel; this form: 12.2 ms, profiles/r04_xt_ncp_kernels.txt.)
-template <class PDE> constexpr int REG_CPW_OF = (pde_has_ncp<PDE>::value && !EXA_REG_NCP_ALIAS) ? 1 : EXA_REG_CPW_DEFAULT;
+// Term sets with a non-conservative product: their three gradient arrays G_d = (D q) / h_d take the place of the sums (StageAReg::GOFF), the node
+// owners evaluate B_d(q) G_d between the gradient and the flux phase.  (Earlier forms -- the products along the pencil, ~290 VGPRs; gradient arrays of
+// their own, one cell per workgroup -- and their numbers: profiles/r04_xt_ncp_kernels.txt, profiles/r05_xt_ncp_kernels.txt.)
 template <int N, class PDE, int CPW, bool FUSE = false>
-__global__ void __launch_bounds__(256 * CPW, ((pde_has_ncp<PDE>::value && !EXA_REG_NCP_ALIAS) ? 1 : 2))
+__global__ void __launch_bounds__(256 * CPW, 2)
 dg_stage_a_reg_kernel(const double* u_in, double* u_out, double* __restrict__ trace,
                       long ncells, CellBox box, double dt, double idx0, double idx1, double idx2, int n_it,
                       const void* __restrict__ ops_raw, const int* __restrict__ tab, const void* __restrict__ step_raw, RegFuse fz, PlainGeo geo) {
@@ -179,7 +149,7 @@ dg_stage_a_reg_kernel(const double* u_in, double* u_out, double* __restrict__ tr
     using SA = StageAReg<N, PDE, CPW>;
     constexpr int NV = SA::NV, NA = SA::NA, DIM = 3;
     constexpr int NN = G::NN, NF = G::NF, SL = G::SL, PX = G::PX, PY = G::PY;
-    constexpr int NT = SA::NT, LS = SA::LS, VS = SA::VS, QSZ = SA::QSZ, SOFF = SA::SOFF, FS = SA::FS, NVA = SA::NVA, PS2 = SA::PS2;
+    constexpr int NT = SA::NT, LS = SA::LS, VS = SA::VS, QSZ = SA::QSZ, SOFF = SA::SOFF, FS = SA::FS, NVA = SA::NVA;
     [[maybe_unused]] constexpr int GOFF = SA::GOFF;
     constexpr bool PUT = SA::PUT;
     constexpr int NIMG = SA::NIMG, NLD = PUT ? NIMG + 1 : NVA;        // a pencil task's loads per node (PUT: + the normal component)
@@ -193,10 +163,7 @@ dg_stage_a_reg_kernel(const double* u_in, double* u_out, double* __restrict__ tr
     // workgroup barrier for LDS data only: the lanes hand nothing to each other through global memory, and the requests for the next cell (u,
     // FUSE: traces) and the u* stores stay in flight across it (__syncthreads() makes every wave wait for all of its vector memory operations)
     auto bar = [&]() {
-#ifndef EXA_REG_FULL_BARRIER
-#define EXA_REG_FULL_BARRIER 0
-#endif
-        if constexpr (FUSE && !EXA_REG_FULL_BARRIER) {
+        if constexpr (FUSE) {
             __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup", "local");
             __builtin_amdgcn_s_barrier();
             __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup", "local");
@@ -208,33 +175,16 @@ dg_stage_a_reg_kernel(const double* u_in, double* u_out, double* __restrict__ tr
     const int o_n = node_lane ? tid : 0;
     const int pk2 = tab[tid], pk1 = tab[NT + tid];
 
-    typedef double d2_t __attribute__((ext_vector_type(2)));
     // K values of one node and level (element index idx = level slot * SL + node) in the array group at `base`
     auto ld_group = [&](int base, int idx, auto& out) {
         constexpr int K = sizeof(out) / sizeof(double);
-        if constexpr (SA::PAIRED) {
 #pragma unroll
-            for (int u = 0; u < K / 2; u++) {
-                const d2_t t2 = *(const __attribute__((address_space(3))) d2_t*)(&lds[base + u * PS2 + 2 * idx]);
-                out[2 * u] = t2.x;
-                out[2 * u + 1] = t2.y;
-            }
-            if constexpr (K % 2 == 1) out[K - 1] = EXA_LD(base + (K / 2) * PS2 + idx);
-        } else {
-#pragma unroll
-            for (int k = 0; k < K; k++) out[k] = EXA_LD(base + k * VS + idx);
-        }
+        for (int k = 0; k < K; k++) out[k] = EXA_LD(base + k * VS + idx);
     };
     auto st_group = [&](int base, int idx, const auto& in) {
         constexpr int K = sizeof(in) / sizeof(double);
-        if constexpr (SA::PAIRED) {
 #pragma unroll
-            for (int u = 0; u < K / 2; u++) *(__attribute__((address_space(3))) d2_t*)(&lds[base + u * PS2 + 2 * idx]) = d2_t{in[2 * u], in[2 * u + 1]};
-            if constexpr (K % 2 == 1) EXA_ST(base + (K / 2) * PS2 + idx, in[K - 1]);
-        } else {
-#pragma unroll
-            for (int k = 0; k < K; k++) EXA_ST(base + k * VS + idx, in[k]);
-        }
+        for (int k = 0; k < K; k++) EXA_ST(base + k * VS + idx, in[k]);
     };
 
     // ---- derive: one pencil task per lane, run-time direction.  s_i = sum_j D[i][j] (1/dx_d) f_d(q_j), even-odd form.
@@ -460,21 +410,17 @@ dg_stage_a_reg_kernel(const double* u_in, double* u_out, double* __restrict__ tr
             }
         }
     };
-    // (-DEXA_REG_SPLIT, CPW == 2: a barrier between the halves, i.e. three segments of similar length per step, the second cell in flight one
-    //  segment behind the first -- measured 9 % SLOWER than two segments: a barrier costs more than the better balance returns,
-    //  profiles/r03_reg_kernel.txt)
-    using M0 = std::integral_constant<int, 0>;                       // derive: the derivative sums (with their gradients G_d where those have arrays of their own)
+    using M0 = std::integral_constant<int, 0>;                       // derive: the derivative sums in one phase (term sets without an ncp)
     using M1 = std::integral_constant<int, 1>;                       // ... only the gradients
-    using M2 = std::integral_constant<int, 2>;                       // ... only the flux sums (GALIAS: the gradients were a phase of their own)
-    constexpr bool GALIAS = SA::GALIAS;
+    using M2 = std::integral_constant<int, 2>;                       // ... only the flux sums (ncp: the gradients were a phase of their own)
     constexpr bool SPLIT_DIR = FXT || !pde_has_dir<PDE>::value;
     auto derive = [&](const Task& tk, const DirFlux<PDE>& fx, const double (&Em)[NE], double tA, double tB, auto mode) {
         // the derive stream is the long one of a step: it gets the SIMD's issue slots ahead of the co-resident wave of the other cell in
         // flight (in its fold / load / closing segment) -- 8 % of the launch (profiles/r03_reg_kernel.txt)
-        __builtin_amdgcn_s_setprio(EXA_REG_PRIO);
+        __builtin_amdgcn_s_setprio(1);
         double e[H][NV], o[H][NV];
         constexpr int MODE = decltype(mode)::value;
-        static_assert(!(GALIAS && MODE == 0), "gradients and sums share their arrays: two phases (M1, owners, M2)");
+        static_assert(!(NCP && MODE == 0), "gradients and sums share their arrays: two phases (M1, owners, M2)");
         if constexpr (MODE != 2) derive_g(tk, Em);
         auto front = [&](auto dc) {                                    // the direction-dependent part: term calls
             if constexpr (MODE != 1) derive_a(dc, tk, fx, e, o, tA, tB);
@@ -489,9 +435,6 @@ dg_stage_a_reg_kernel(const double* u_in, double* u_out, double* __restrict__ tr
             front(std::integral_constant<int, -1>{});
         }
         if constexpr (MODE != 1) {
-#ifdef EXA_REG_SPLIT
-            if constexpr (CPW == 2) bar();
-#endif
             derive_b(tk, Em, e, o);                                    // the contraction is the same for every direction
         }
         __builtin_amdgcn_s_setprio(0);
@@ -577,11 +520,9 @@ dg_stage_a_reg_kernel(const double* u_in, double* u_out, double* __restrict__ tr
         }
     }
     fetch_faces(cx, cy, cz);
-#ifndef EXA_REG_LOCKSTEP
     if constexpr (CPW == 2) {
         if (half == 1) bar();                                // the second half runs one barrier (= one phase) behind the first
     }
-#endif
 
     // FUSE: u* of the cell just finished is stored during the next cell (see there); the plain predictor stores it at once and keeps
     // __syncthreads() (measured: deferring it there costs 1 %, 158.4 against 156.9 ms per 128^3 launch)
@@ -701,12 +642,12 @@ dg_stage_a_reg_kernel(const double* u_in, double* u_out, double* __restrict__ tr
             EXA_STAMP(0);
             bar();
             EXA_STAMP(1);
-            [[maybe_unused]] double nd0[NV];                               // GALIAS: the owner's ncp term of iteration 0
+            [[maybe_unused]] double nd0[NV];                               // ncp: the owner's ncp term of iteration 0
             {
                 Task tk1;
                 DirFlux<PDE> fx1(0, 0.0);
                 decode(opaque_v(pk1), tk1, fx1);
-                if constexpr (GALIAS) {                                    // gradients | owners | flux sums
+                if constexpr (NCP) {                                    // gradients | owners | flux sums
                     derive(tk1, fx1, Em, 0.0, 0.0, M1{});
                     bar();
                     if (owner) ncp_at_owner(un, 0, 0, nd0);
@@ -737,15 +678,8 @@ dg_stage_a_reg_kernel(const double* u_in, double* u_out, double* __restrict__ tr
                     for (int v = 0; v < NV; v++) S[v] -= Sq[v];
                 }
                 if constexpr (NCP) {                                       // + sum_d B_d(q) (D q) / h_d
-                    double nd[NV];
-                    if constexpr (GALIAS) {
     #pragma unroll
-                        for (int v = 0; v < NV; v++) nd[v] = nd0[v];
-                    } else {
-                        ncp_at_owner(un, 0, 0, nd);
-                    }
-    #pragma unroll
-                    for (int v = 0; v < NV; v++) S[v] += nd[v];
+                    for (int v = 0; v < NV; v++) S[v] += nd0[v];
                 }
     #pragma unroll
                 for (int l = 0; l < N; l++)
@@ -775,17 +709,14 @@ dg_stage_a_reg_kernel(const double* u_in, double* u_out, double* __restrict__ tr
         // (held over them, the fused kernel spilled 8 registers there)
         if constexpr (PUT) decode(opaque_v(pk2), tk2, fx2);
         if (n_it > IT0 && owner) load_levels(std::integral_constant<int, 0>{}, q);
-        // r5 (EXA_REG_DEFER_FOLD: 0 never, 1 term sets with an ncp or with terms that see x, t (default), 2 every term set): the time contraction of an iteration DEFERRED to its end, as in
+        // r5, term sets with an ncp or with terms that see x, t: the time contraction of an iteration DEFERRED to its end, as in
         // exa_dg_m8.hpp -- a fold only keeps S_x + S_y + S_z (+ source / ncp terms) of its two levels; the owner state in front of the derive phases is
         // the levels not yet in LDS + the sums so far (30 doubles) instead of iterate + accumulators (60).  That is what lets the ncp variant, whose owners
         // hold their products over the flux phase, run two cells per CU under the 256-VGPR cap (108 spilled registers with the immediate fold).
-#ifndef EXA_REG_DEFER_FOLD
-#define EXA_REG_DEFER_FOLD 1
-#endif
         // Measured (r5, profiles/r05_xt_ncp_kernels.txt): ncp 11.8 -> 10.1 ms per 32^3 launch (with the two cells per CU it allows), x,t source 6.09 -> 5.91;
         // the built-in Euler set LOSES 15 % (175.6 against 152.3 ms per 128^3 launch: no spills to win back, and the contraction of a whole iteration in ONE
         // fold unbalances the two cells in flight, whose folds run beside each other's derive phases) -- hence not for term sets of the state alone.
-        constexpr bool DEFER_FOLD = EXA_REG_DEFER_FOLD == 2 || (EXA_REG_DEFER_FOLD == 1 && (NCP || XT));
+        constexpr bool DEFER_FOLD = NCP || XT;
         for (int it = IT0; it < n_it; it++) {
             double acc[N][NV];
             [[maybe_unused]] double Sk[DEFER_FOLD ? N : 1][NV];
@@ -798,8 +729,8 @@ dg_stage_a_reg_kernel(const double* u_in, double* u_out, double* __restrict__ tr
                 bar();
                 EXA_STAMP(6);
                 static_assert(NL == 2, "odd N: the last step of an iteration has one level -- mask the tasks of level slot 1");
-                [[maybe_unused]] double ndk[NL][NV];                   // GALIAS: the owner's ncp terms of the step's levels
-                if constexpr (GALIAS) {                                // gradients | owners: B_d(q) G_d | flux sums (into the arrays the gradients held)
+                [[maybe_unused]] double ndk[NL][NV];                   // ncp: the owner's ncp terms of the step's levels
+                if constexpr (NCP) {                                // gradients | owners: B_d(q) G_d | flux sums (into the arrays the gradients held)
                     derive(tk2, fx2, Em, XT ? level_t(l0) : 0.0, XT ? level_t(l0 + 1) : 0.0, M1{});
                     bar();
                     if (owner) {
@@ -850,19 +781,11 @@ dg_stage_a_reg_kernel(const double* u_in, double* u_out, double* __restrict__ tr
                             for (int v = 0; v < NV; v++) Sx[ls][v] -= Sq[v];
                         }
                     }
-                    if constexpr (NCP) {                               // + sum_d B_d(q_l) G_d: the gradients the derive phase left, the state from registers
+                    if constexpr (NCP) {                               // + sum_d B_d(q_l) G_d, evaluated by the owners between the two derive phases
 #pragma unroll
-                        for (int ls = 0; ls < NL; ls++) {
-                            double nd[NV];
-                            if constexpr (GALIAS) {
+                        for (int ls = 0; ls < NL; ls++)
 #pragma unroll
-                                for (int v = 0; v < NV; v++) nd[v] = ndk[ls][v];
-                            } else {
-                                ncp_at_owner(q[l0 + ls], ls, l0 + ls, nd);
-                            }
-#pragma unroll
-                            for (int v = 0; v < NV; v++) Sx[ls][v] += nd[v];
-                        }
+                            for (int v = 0; v < NV; v++) Sx[ls][v] += ndk[ls][v];
                     }
                     if constexpr (DEFER_FOLD) {
 #pragma unroll
@@ -1073,11 +996,9 @@ dg_stage_a_reg_kernel(const double* u_in, double* u_out, double* __restrict__ tr
             for (int v = 0; v < NV; v++) uo[v] = upend[v];
         }
     }
-#ifndef EXA_REG_LOCKSTEP
     if constexpr (CPW == 2) {
         if (half == 0) bar();                                // (the barrier the second half is behind)
     }
-#endif
     EXA_STAMP_FLUSH();
 }
 

@@ -96,10 +96,7 @@ template <int N, class PDE, int HS, int OH> struct StageAStream {
     // Levels per slot whose new iterate stays in registers over the iteration boundary (the others wait in the slab).
     // 1: 6 of 8 levels in the slab (120 KiB per workgroup, 3.84 MB per XCD: the cyclic sweep just misses the 4 MB L2 --
     // 47 GB of L2 <-> fabric traffic per 32^3-cell launch against 2.35 GB algorithmic); 2: 4 levels (80 KiB, 2.56 MB per XCD).
-#ifndef EXA_STREAM_KEEP
-#define EXA_STREAM_KEEP 2
-#endif
-    static constexpr int KEEP = (OH == 1 && LS >= 2) ? EXA_STREAM_KEEP : 1;
+    static constexpr int KEEP = (OH == 1 && LS >= 2) ? 2 : 1;
     static_assert(HS == 1 || HS == 2, "HS");
     static_assert(OH == 1 || OH == 2, "OH");
 };
@@ -409,11 +406,7 @@ dg_stage_a_stream_kernel(const double* __restrict__ u_in, double* __restrict__ u
                     }
                 }
                 EXA_STAMP(6);
-#ifdef EXA_STREAM_BARRIER4
-                __syncthreads();
-#else
-                static_assert(OH == 1, "two owners per node: the fold reads the co-owner's slot -- build with -DEXA_STREAM_BARRIER4");
-#endif
+                static_assert(OH == 1, "two owners per node: the fold reads the co-owner's slot -- it needs a barrier here");
                 // (no barrier here: the next load phase writes Q and the flux scalars at the owner's OWN node, which only this lane
                 //  read in the fold above; the derive phase that read them across lanes ended two barriers ago)
                 EXA_STAMP(7);
@@ -450,9 +443,7 @@ dg_stage_a_stream_kernel(const double* __restrict__ u_in, double* __restrict__ u
         }
 
         // ---- time averages: each owner over its levels (OH == 2: the two parts meet in LDS): qbar | Fbar_d
-#ifndef EXA_STREAM_BARRIER4
         __syncthreads();                                         // the last fold of every lane is done: the final image reuses Q / A / B
-#endif
         {
             double qb[NV], Fb[DIM][NV];
             [[maybe_unused]] double Sbar[NV];

@@ -8,7 +8,7 @@
 #include "exa_lim_detect.hpp"      // EXA_LIM_CASES
 #include "exa_pde.hpp"
 
-// F* must be stage B's to rounding: the eigenvalue member is the one exa_dg_kernels.hpp picks with this macro (same default)
+// F* must be stage B's to rounding: stage B (exa_dg_kernels.hpp) takes the IEEE eigenvalue member `maxeig`, which is this macro's default here
 #ifndef EXA_STAGE_B_FAST_EIG
 #define EXA_STAGE_B_FAST_EIG 0
 #endif

@@ -268,7 +268,7 @@ class HIPPrinter(CodePrinter):
         if k.dim == 3 and N == 8:
             return "dg_stage_a_m8_kernel (iterate in registers, derivative contraction on v_mfma_f64_4x4x4_4b_f64)"
         if k.dim == 3 and N == 7:
-            return "dg_stage_a_stream_kernel<7> (level-streamed)"
+            return "dg_stage_a_stream_kernel (level-streamed, N = 7)"
         return "dg_stage_a_kernel<%d,%d>" % (k.dim, N)
 
     def _plan_text(self, stage_a=None):

@@ -85,6 +85,37 @@ def test_stage_a_variants_agree_on_boxes(exa):
     assert not np.array_equal(out["reg"][0], u)
 
 
+RESERVE_CASES = [(6, (3, 2, 2), "reg"), (6, (3, 2, 2), "lds"), (8, (2, 2, 1), "reg")]
+_reserve_ref = {}
+
+
+def _reserve_case(order, nc):
+    """input and oracle of a reserve case, computed once per (order, cells) and left unchanged"""
+    if (order, nc) not in _reserve_ref:
+        u, dx, dt = (C.variant_n6_input if order == 6 else C.variant_n8_input)(nc, -1)
+        _reserve_ref[order, nc] = (u, dx, dt, DgRef(u, dt, dx, 3, order, nc, order))
+    return _reserve_ref[order, nc]
+
+
+@pytest.mark.parametrize("order,nc,variant", RESERVE_CASES)
+def test_stage_a_reserve_clamps_the_persistent_grid(exa, orc, order, nc, variant):
+    """exa_dg_plan_set_stage_a_reserve keeps the persistent grids that many workgroups below what the chip holds, at least one: with a
+    reserve beyond any chip ONE workgroup walks all cells.  The arithmetic of a cell does not depend on which workgroup takes it, so u* and
+    the traces are those of the unreserved launch bit for bit, and both are within the oracle's bound."""
+    u, dx, dt, r = _reserve_case(order, nc)
+    s = exa.AderDgSolver(3, order, nc, dx=dx, stage_a=variant)
+    out = []
+    for reserve in (0, 10 ** 6):
+        s.set_reserve_cus(reserve)
+        s.trace.zero_()
+        s.upload(u)
+        s.predictor_volume(dt)
+        out.append((s.download().copy(), s.trace.cpu().numpy().copy()))
+        r.check_ustar(out[-1][0], what="u* (reserve %d)" % reserve)
+        r.check_traces(out[-1][1], what="traces (reserve %d)" % reserve)
+    assert np.array_equal(out[0][0], out[1][0]) and np.array_equal(out[0][1], out[1][1])
+
+
 def test_stage_a_variant_rejects_unknown(exa):
     from exahype_amd._lib import ExaHypeHipError
     s = exa.AderDgSolver(3, 4, (1, 1, 1))
