@@ -97,6 +97,8 @@ template <int N, class PDE, int HS, int OH> struct StageAStream {
     // 1: 6 of 8 levels in the slab (120 KiB per workgroup, 3.84 MB per XCD: the cyclic sweep just misses the 4 MB L2 --
     // 47 GB of L2 <-> fabric traffic per 32^3-cell launch against 2.35 GB algorithmic); 2: 4 levels (80 KiB, 2.56 MB per XCD).
     static constexpr int KEEP = (OH == 1 && LS >= 2) ? 2 : 1;
+    // two levels of Q, A, B (+ cached scalars) in LDS: 6 variables at N = 8 need 165 888 B, 8 variables 221 184 B -- the selector refuses those (dg_inst.hip)
+    static constexpr bool FITS = LDS_BYTES <= 160 * 1024 && NT <= 1024;
     static_assert(HS == 1 || HS == 2, "HS");
     static_assert(OH == 1 || OH == 2, "OH");
 };
