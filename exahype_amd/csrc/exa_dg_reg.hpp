@@ -21,8 +21,9 @@
 //   before the next barrier).
 //
 // LDS image: [slot][level slot][node], node stride 1, level stride SL = 217 (odd), slot stride 2 SL; slots = NV of q, NAUX
-// scalars, 3 x NV sums.  Which lane takes which pencil comes from host-built tables behind the operator image
-// (dg_inst.hip fill_reg_tables; model and search: scripts/reg_tables.py): six of the eight 32-lane groups hold pencils of ONE
+// scalars, 3 x NV sums; the closing image (time averages, volume terms) lies in the arrays of the sums (StageAReg::FS).
+// Which lane takes which pencil comes from host-built tables behind the operator image (dg_inst.hip fill_reg_tables; model
+// and search: scripts/reg_tables.py): six of the eight 32-lane groups hold pencils of ONE
 // direction with pairwise distinct bank residues (the x pencils of a level are 36 consecutive doubles; the z pencils start
 // on even doubles, so a group takes 16 of each level -- the odd level stride interleaves them), the remaining pencils share
 // the last groups with a few 2-way conflicts.
@@ -74,6 +75,13 @@ template <class P> struct pde_nput<P, true> { static constexpr int value = P::NP
 #ifndef EXA_REG_CPW
 #define EXA_REG_CPW 2                          // cells in flight per workgroup: 2 = one 512-thread workgroup per CU, halves one barrier apart (128^3 cells:
 #endif                                         // 154.5 ms; 1 = two 256-thread workgroups: 158.9 ms)
+#ifndef EXA_REG_OFFSET
+#define EXA_REG_OFFSET 1                       // CPW = 2: barriers the second half of the workgroup runs behind the first.  An experiment's knob: only 1
+#endif                                         // keeps one half's derive beside the other's fold / closing phases in EVERY cell.
+// An odd offset is necessary for that pairing (asserted), not sufficient: a cell of the plain instantiation has 35 barriers, an odd number, so any offset but 1
+// pairs derive with derive in every second cell.  9 and 17 were measured with the stand-alone bench (scripts/bench_reg.hip), on a 34-barrier form of the cell
+// where odd does suffice, not with the benchmark: 1.4 % and 1.9 % slower than 1 (profiles/reg_kernel_closing_schedule.txt).
+static_assert(EXA_REG_OFFSET > 0 && EXA_REG_OFFSET % 2 == 1, "EXA_REG_OFFSET: odd, or the two cells in flight derive at the same time");
 
 template <int N> struct RegGeo {
     static constexpr int NN = N * N * N, NF = N * N;
@@ -110,9 +118,14 @@ template <int N, class PDE, int CPW = 1> struct StageAReg {
     static constexpr int SOFF = NIMG * VS;                            // S_d at SOFF + d * QSZ
     static constexpr int GOFF = SOFF;                                 // (ncp: the gradients G_d, in the arrays of the sums)
     static constexpr int PIC_D = SOFF + 3 * QSZ;
-    static constexpr int FS = G::NN;                                  // closing phases: [array][var][node], arrays qbar | Fbar_x | Fbar_y | Fbar_z (| source)
-    static constexpr int FIN_D = (pde_has_source<PDE>::value ? 5 : 4) * NV * FS;
-    static constexpr int CELL_D = PIC_D > FIN_D ? PIC_D : FIN_D;      // doubles of LDS per cell in flight
+    // closing phases: [array][var][node], arrays qbar | Fbar_x | Fbar_y | Fbar_z (| source), IN the region of the sums -- the three sum arrays
+    // SOFF + d QSZ + v VS + ls SL + node are 6 NV consecutive arrays of stride SL (VS = 2 SL), closing array j takes the j-th of them.  An owner's
+    // entries of the closing image are then exactly its entries of the sums (j SL + n = a SL + m with n, m < SL forces j = a, n = m), and the closing
+    // image never touches the put image [0, SOFF): what that buys is said at the end of the cell loop, where a barrier is gone.
+    static constexpr int FS = G::SL;
+    static constexpr int FIN_D = SOFF + (pde_has_source<PDE>::value ? 5 : 4) * NV * FS;
+    static_assert(FIN_D <= PIC_D && G::NN <= G::SL, "the closing image lies inside the arrays of the sums");
+    static constexpr int CELL_D = PIC_D;                              // doubles of LDS per cell in flight
     static constexpr size_t LDS_BYTES = sizeof(double) * ((size_t)CELL_D * CPW + 2 * 3 * N);   // + the one-kernel step's corrector weights
     static constexpr bool FITS = G::NN <= NT && 2 * sizeof(double) * (size_t)CELL_D + 2048 <= 160 * 1024;
     // behind the image of dg_stage_a_kernel (StageA<3, N, PDE, CPB>::IMAGE_BYTES): lane -> packed derive task of a two-level
@@ -151,6 +164,7 @@ dg_stage_a_reg_kernel(const double* u_in, double* u_out, double* __restrict__ tr
     constexpr int NN = G::NN, NF = G::NF, SL = G::SL, PX = G::PX, PY = G::PY;
     constexpr int NT = SA::NT, LS = SA::LS, VS = SA::VS, QSZ = SA::QSZ, SOFF = SA::SOFF, FS = SA::FS, NVA = SA::NVA;
     [[maybe_unused]] constexpr int GOFF = SA::GOFF;
+    constexpr int CB = SOFF;                                          // the closing image: in the arrays of the sums (StageAReg::FS)
     constexpr bool PUT = SA::PUT;
     constexpr int NIMG = SA::NIMG, NLD = PUT ? NIMG + 1 : NVA;        // a pencil task's loads per node (PUT: + the normal component)
     constexpr int H = N / 2;
@@ -521,7 +535,10 @@ dg_stage_a_reg_kernel(const double* u_in, double* u_out, double* __restrict__ tr
     }
     fetch_faces(cx, cy, cz);
     if constexpr (CPW == 2) {
-        if (half == 1) bar();                                // the second half runs one barrier (= one phase) behind the first
+        if (half == 1) {                                     // the second half runs EXA_REG_OFFSET barriers (= phases) behind the first
+#pragma unroll 1
+            for (int k = 0; k < EXA_REG_OFFSET; k++) bar();
+        }
     }
 
     // FUSE: u* of the cell just finished is stored during the next cell (see there); the plain predictor stores it at once and keeps
@@ -859,8 +876,12 @@ dg_stage_a_reg_kernel(const double* u_in, double* u_out, double* __restrict__ tr
                 }
             });
         }
-        // ---- time averages (A.3): qbar | Fbar_x | Fbar_y | Fbar_z (| time-averaged source), node-major images of stride FS
-        bar();                                               // every fold has read its sums: the closing image reuses the LDS
+        // ---- time averages (A.3): qbar | Fbar_x | Fbar_y | Fbar_z (| time-averaged source), node-major images of stride FS at CB
+        // The barrier in front of them protects nothing any more: the owners write the entries of THEIR node in the arrays at SOFF, and since the last
+        // barrier only the owners have read those arrays, each the entries of its own node (the last fold; n_it = 1: the fold of iteration 0).  It stays
+        // because it pays: without it the averages (arithmetic, as long as a Picard phase) lengthen the last fold's interval beside the other cell's
+        // derive instead of running beside its fold -- measured 1.4 ms per 128^3 launch slower (profiles/reg_kernel_closing_schedule.txt).
+        bar();
         if (owner) {
             double wm[N];
             sload<N>(ops_here<N>(ops_raw)->w, wm);
@@ -903,10 +924,10 @@ dg_stage_a_reg_kernel(const double* u_in, double* u_out, double* __restrict__ tr
             }
 #pragma unroll
             for (int v = 0; v < NV; v++) {
-                EXA_ST(v * FS + o_n, qb[v]);
+                EXA_ST(CB + v * FS + o_n, qb[v]);
 #pragma unroll
-                for (int d = 0; d < DIM; d++) EXA_ST(((1 + d) * NV + v) * FS + o_n, Fb[d][v]);
-                if constexpr (pde_has_source<PDE>::value) EXA_ST((4 * NV + v) * FS + o_n, Sbar[v]);
+                for (int d = 0; d < DIM; d++) EXA_ST(CB + ((1 + d) * NV + v) * FS + o_n, Fb[d][v]);
+                if constexpr (pde_has_source<PDE>::value) EXA_ST(CB + (4 * NV + v) * FS + o_n, Sbar[v]);
             }
         }
         EXA_STAMP(10);
@@ -937,13 +958,13 @@ dg_stage_a_reg_kernel(const double* u_in, double* u_out, double* __restrict__ tr
                     double qb[N], Fb[N], vol[N];
 #pragma unroll
                     for (int j = 0; j < N; j++) {
-                        qb[j] = EXA_LD(v * FS + pb + j * ps);
-                        Fb[j] = EXA_LD(((1 + D) * NV + v) * FS + pb + j * ps);
+                        qb[j] = EXA_LD(CB + v * FS + pb + j * ps);
+                        Fb[j] = EXA_LD(CB + ((1 + D) * NV + v) * FS + pb + j * ps);
                     }
                     eo_apply<N>(KE, Fb, vol);
                     const double sc = dt * (D == 0 ? idx0 : (D == 1 ? idx1 : idx2));
 #pragma unroll
-                    for (int i = 0; i < N; i++) EXA_ST(((1 + D) * NV + v) * FS + pb + i * ps, sc * iwm[i] * vol[i]);
+                    for (int i = 0; i < N; i++) EXA_ST(CB + ((1 + D) * NV + v) * FS + pb + i * ps, sc * iwm[i] * vol[i]);
                     double qL = 0.0, qR = 0.0, FL = 0.0, FR = 0.0;
 #pragma unroll
                     for (int j = 0; j < N; j++) {
@@ -973,9 +994,9 @@ dg_stage_a_reg_kernel(const double* u_in, double* u_out, double* __restrict__ tr
             for (int v2 = 0; v2 < NV; v2++) {
                 us[v2] = ukeep[v2];
                 if constexpr (NCP) us[v2] -= dt * pw[v2];
-                if constexpr (pde_has_source<PDE>::value) us[v2] += dt * EXA_LD((4 * NV + v2) * FS + o_n);
+                if constexpr (pde_has_source<PDE>::value) us[v2] += dt * EXA_LD(CB + (4 * NV + v2) * FS + o_n);
 #pragma unroll
-                for (int d = 0; d < DIM; d++) us[v2] += EXA_LD(((1 + d) * NV + v2) * FS + o_n);
+                for (int d = 0; d < DIM; d++) us[v2] += EXA_LD(CB + ((1 + d) * NV + v2) * FS + o_n);
             }
             if constexpr (DEFER) {
 #pragma unroll
@@ -987,7 +1008,13 @@ dg_stage_a_reg_kernel(const double* u_in, double* u_out, double* __restrict__ tr
             }
         }
         if constexpr (DEFER) pend_cell = active ? cell : -1;
-        bar();                                               // LDS is reused by the next cell
+        // No barrier at the end of the cell.  Readers still at work: the owners' u* loads above, each at its own node in the arrays at SOFF.  What follows
+        // is the next cell's put of iteration 0, which writes only [0, SOFF) -- nobody has read that region since the last derive phase, four barriers
+        // back -- and then a barrier; the first store into the arrays at SOFF (the sums of iteration 0's derive) comes after that barrier, every lane's
+        // u* loads before it in program order, and a wave's LDS loads have returned when it passes a barrier.  So u* and the next put share an interval.
+        // Kept for the one-kernel step, whose prologue writes LAM / FSO at SOFF at the top of the cell, and (unchecked) for term sets that see x, t.
+        constexpr bool END_BAR = FUSE || XT;
+        if constexpr (END_BAR) bar();                        // LDS is reused by the next cell
     }
     if constexpr (DEFER) {
         if (node_lane && pend_cell >= 0) {
@@ -997,7 +1024,10 @@ dg_stage_a_reg_kernel(const double* u_in, double* u_out, double* __restrict__ tr
         }
     }
     if constexpr (CPW == 2) {
-        if (half == 0) bar();                                // (the barrier the second half is behind)
+        if (half == 0) {                                     // (the barriers the second half is behind)
+#pragma unroll 1
+            for (int k = 0; k < EXA_REG_OFFSET; k++) bar();
+        }
     }
     EXA_STAMP_FLUSH();
 }

@@ -66,12 +66,15 @@ int main(int argc, char** argv) {
 #if BN == 8
                 const char* names[12] = {"it0 load", "it0 barrier", "it0 derive", "it0 fold", "(fold tail)", "barrier", "derive", "fold+load", "averages", "vol+traces", "u* store", "-"};
 #else
-                const char* names[12] = {"it0 load", "it0 barrier", "it0 derive", "it0 barrier", "it0 fold", "load", "barrier", "derive", "barrier", "fold", "averages", "vol+traces"};
+                // one stamp per interval outside the Picard loop, each with the barrier in front of it: u* and the next cell's put share one (slot 0),
+                // averages (slot 10), volume + traces (slot 11).  (The in-kernel stamp points kept their numbers.  This program runs the plain kernel; in
+                // the one-kernel step and for x, t term sets, which keep the barrier at the end of the cell, slot 0 spans two intervals: u*, then the put.)
+                const char* names[12] = {"u*+it0 put", "it0 barrier", "it0 derive", "it0 barrier", "it0 fold", "load", "barrier", "derive", "barrier", "fold", "averages", "vol+traces"};
 #endif
                 printf("cycles per cell (waves 0..3):\n");
                 double tot[4] = {0};
                 for (int k = 0; k < 12; k++) { printf("   %-12s", names[k]); for (int w = 0; w < 4; w++) { printf(" %9.0f", (double)z[w * 12 + k] / ncells); tot[w] += (double)z[w * 12 + k] / ncells; } printf("\n"); }
-                printf("   %-12s %9.0f %9.0f %9.0f %9.0f   (u* store and the cell-loop overhead are in 'it0 load')\n", "total", tot[0], tot[1], tot[2], tot[3]);
+                printf("   %-12s %9.0f %9.0f %9.0f %9.0f   (the cell-loop overhead is in 'u*+it0 put')\n", "total", tot[0], tot[1], tot[2], tot[3]);
             }
 #endif
         }

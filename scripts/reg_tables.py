@@ -14,7 +14,8 @@ directions: `library_table` restates the constructive tables of dg_inst.hip fill
 step of a table under either image, the second read included.
 
 usage: reg_tables.py [N] [iters]        the search
-       reg_tables.py model              modelled conflict cycles per step of the shipped table, both images
+       reg_tables.py model              modelled conflict cycles per step of the shipped table, both images, and of the closing phases'
+                                        volume rounds for the array strides 216 and 217 of the closing image (volume_cost)
 """
 import random
 import sys
@@ -159,6 +160,24 @@ def step_cost(assign, put):
     return dict(same=same, vn=vn, wr=wr, total=same + vn + wr)
 
 
+def volume_cost(FS):
+    """Modelled extra LDS cycles of the closing phases' volume rounds of one cell (exa_dg_reg.hpp: one round per direction, lane = task (v, t), t
+    fastest, NV * NF of the 256 lanes at work) for a closing image [array][variable][node] of array stride FS, as a dict: `rd` = the loads of qbar
+    and Fbar_d (12 per lane and round; the two arrays lie a common shift apart, which changes no conflict), `wr` = the stores of the volume terms (6).
+    Same measure as step_cost: cycles beyond the 2 (reads) or 6 (writes) a wave instruction takes without a conflict."""
+    PY, PX, _ = library_geometry()
+    ps, pbase, _ = geometry(PY, PX, 0)
+    rd = wr = 0
+    for w in range(4):
+        lanes = [tid if tid < NV * NF else None for tid in range(64 * w, 64 * w + 64)]
+        for d in range(3):
+            for jj in range(N):
+                a = [None if tid is None else (tid // NF) * FS + pbase(d, tid % NF) + jj * ps[d] for tid in lanes]
+                rd += 2 * max(0, group_cost(a, 32, 32) - 2)
+                wr += max(0, group_cost(a, 16, 16) - 6)
+    return dict(rd=rd, wr=wr, total=rd + wr)
+
+
 def mixed_groups(assign):
     """the 32-lane groups of a table that hold pencils of more than one direction"""
     return [g for g in range(len(assign) // 32) if len({t[0] for t in assign[32 * g:32 * g + 32] if t is not None}) > 1]
@@ -228,6 +247,8 @@ if __name__ == "__main__" and ARGS[:1] == ["model"]:
     print("shipped table, two-level step: groups that mix directions %s" % mixed_groups(tab))
     print("image q | 1/rho | p : modelled extra LDS cycles per step %s" % old)
     print("primitive image     : modelled extra LDS cycles per step %s" % new)
+    for FS in (NN, library_geometry()[2]):
+        print("volume rounds, closing image of array stride %d: modelled extra LDS cycles per cell %s" % (FS, volume_cost(FS)))
     sys.exit(0)
 if __name__ == "__main__":
     cands = []
