@@ -12,6 +12,7 @@ LIB_PATH = os.path.join(HERE, "lib", "libexahype_hip.so")
 PDE_EULER_REF2D, PDE_EULER, PDE_ADVECTION = 0, 1, 2
 FV_FAITHFUL, FV_RUSANOV, FV_MUSCL_HANCOCK = 0, 1, 2         # include/exahype_hip.h EXA_FV_*
 FV_FACE_PERIODIC, FV_FACE_STATE, FV_FACE_MIRROR = 0, 1, 2      # include/exahype_hip.h EXA_FV_FACE_*
+PDE_FLAG_XT, PDE_FLAG_NCP, PDE_FLAG_ADMISSIBLE, PDE_FLAG_CONSERVATIVE, PDE_FLAG_MUSCL_HANCOCK = 1, 2, 4, 8, 16      # EXA_PDE_FLAG_*
 
 # every symbol include/exahype_hip.h declares: (restype, argtypes)
 _vp, _dp, _lp = C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_long)
@@ -62,6 +63,9 @@ SIGNATURES = {
     "exa_lim_face_layer_count": (C.c_long, [_vp, C.c_int]),
     "exa_lim_face_layers": (C.c_int, [_vp, _vp, C.c_int, C.c_int, _vp, _vp, _vp]),
     "exa_dg_reconstruct_patches": (C.c_int, [_vp, _vp, _vp, C.c_long, _vp, _vp]),
+    "exa_lim_patch_count_halo": (C.c_long, [_vp, C.c_int]),
+    "exa_lim_project_patches_halo2": (C.c_int, [_vp, _vp, _vp, C.c_long, _vp, C.POINTER(C.c_int), _vp, _vp]),
+    "exa_lim_reconstruct_patches_halo": (C.c_int, [_vp, _vp, _vp, C.c_long, _vp, C.c_int, _vp]),
     "exa_lim_bounds_count": (C.c_long, [_vp]),
     "exa_lim_snapshot": (C.c_int, [_vp, _vp, _vp, _vp, _vp]),
     "exa_lim_detect": (C.c_int, [_vp, _vp, _vp, C.POINTER(_vp), C.POINTER(C.c_int), C.c_double, C.c_double, C.c_double, _vp, _vp]),

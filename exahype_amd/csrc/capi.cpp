@@ -762,6 +762,47 @@ int exa_dg_reconstruct_patches(exa_dg_plan* p, const double* patch_dev, const lo
                                static_cast<const double*>(p->ops.lim) + (size_t)p->N * Ns, (hipStream_t)stream);
 }
 
+/* ---- patches with halo 2: what the second-order patch update (EXA_FV_MUSCL_HANCOCK) reads ---- */
+
+long exa_lim_patch_count_halo(const exa_dg_plan* p, int halo) {
+    if (!p || (halo != 1 && halo != 2)) { set_error("exa_lim_patch_count_halo: %s", !p ? "NULL plan" : "halo must be 1 or 2"); return EXA_ERR_INVALID; }
+    return lpow(2 * p->N - 1 + 2 * halo, p->dim) * p->nv;
+}
+
+int exa_lim_project_patches_halo2(exa_dg_plan* p, const double* u_dev, const long* cells_dev, long n, double* patch_dev, const int* face_kind,
+                                  const double* face_data_dev, void* stream) {
+    if (!p || !u_dev || (n > 0 && (!cells_dev || !patch_dev)) || n < 0) { set_error("exa_lim_project_patches_halo2: bad argument"); return EXA_ERR_INVALID; }
+    if (face_kind)
+        for (int f = 0; f < 2 * p->dim; f++) {
+            if (face_kind[f] < EXA_FV_FACE_PERIODIC || face_kind[f] > EXA_FV_FACE_MIRROR) {
+                set_error("exa_lim_project_patches_halo2: face_kind[%d] = %d is not EXA_FV_FACE_PERIODIC, _STATE or _MIRROR", f, face_kind[f]);
+                return EXA_ERR_INVALID;
+            }
+            if (face_kind[f] != EXA_FV_FACE_PERIODIC && !face_data_dev) {
+                set_error("exa_lim_project_patches_halo2: face %d is not periodic and face_data_dev is NULL", f);
+                return EXA_ERR_INVALID;
+            }
+        }
+    int rc = use_device(p->device);
+    if (rc) return rc;
+    rc = lim_tables(p);
+    if (rc) return rc;
+    return limiter_project_halo2(p->dim, p->N, p->nv, p->nc, u_dev, cells_dev, n, patch_dev, static_cast<const double*>(p->ops.lim), face_kind,
+                                 face_kind ? face_data_dev : nullptr, (hipStream_t)stream);
+}
+
+int exa_lim_reconstruct_patches_halo(exa_dg_plan* p, const double* patch_dev, const long* cells_dev, long n, double* u_dev, int halo, void* stream) {
+    if (!p || !u_dev || (n > 0 && (!cells_dev || !patch_dev)) || n < 0) { set_error("exa_lim_reconstruct_patches_halo: bad argument"); return EXA_ERR_INVALID; }
+    if (halo != 1 && halo != 2) { set_error("exa_lim_reconstruct_patches_halo: halo = %d, the patches have halo 1 or 2", halo); return EXA_ERR_INVALID; }
+    int rc = use_device(p->device);
+    if (rc) return rc;
+    rc = lim_tables(p);
+    if (rc) return rc;
+    const int Ns = 2 * p->N - 1;
+    return limiter_reconstruct_halo(p->dim, p->N, Ns, p->nv, patch_dev, cells_dev, n, u_dev, static_cast<const double*>(p->ops.lim) + (size_t)p->N * Ns, halo,
+                                    (hipStream_t)stream);
+}
+
 // the registered term set of the plan if it carries its own criterion (EXA_PDE_FLAG_ADMISSIBLE), else null
 static const UserPde* lim_user(const exa_dg_plan* p) {
     if (p->pde < 100 || p->pde - 100 >= (int)g_user.size()) return nullptr;

@@ -5,6 +5,9 @@
 //                               subcell layer of the face neighbours' projections (periodic in the block), edge
 //                               and corner halo entries = nearest interior value (never read by the 7-point stencil)
 //   limiter_reconstruct_kernel  FV patch interior -> DG nodes: u = (R x R x R) v
+// and, for the second-order patch update (exa_fv_muscl.hpp: halo_size = 2, reads the edge entries),
+//   limiter_project_halo2_kernel  troubled cell -> FV patch with halo 2: face halos two layers deep, edge entries from the diagonal
+//                               cells, mirror / state domain faces (further down); the reconstruction kernels are templates over the halo
 // One workgroup per troubled cell.  Five-variable systems take the all-variables kernels further down (AoS runs, 28 barriers per cell);
 // the kernels here (other variable counts) run the tensor products variable by variable through two LDS buffers.  The kernels are
 // instantiated per order (N, N_s compile-time): with run-time extents every output element paid three integer divisions
@@ -181,7 +184,7 @@ limiter_face_layers_kernel(int, int, int nv, long nc0, long nc1, long nc2, const
     }
 }
 
-template <int DIM, int N>
+template <int DIM, int N, int H = 1>
 __global__ void __launch_bounds__(256)
 limiter_reconstruct_kernel(int, int, int nv, const double* __restrict__ patch, const long* __restrict__ cells,
                            double* __restrict__ u, const double* __restrict__ R) {
@@ -189,7 +192,7 @@ limiter_reconstruct_kernel(int, int, int nv, const double* __restrict__ patch, c
     constexpr int Ns = 2 * N - 1;
     const long cell = cells[blockIdx.x];
     if (cell < 0) return;                                          // empty slot
-    const int S = Ns + 2;
+    const int S = Ns + 2 * H;
     long NN = 1, SS = 1, NsD = 1;
     for (int a = 0; a < DIM; a++) { NN *= N; SS *= S; NsD *= Ns; }
     const double* pt = patch + (long)blockIdx.x * SS * nv;
@@ -197,7 +200,7 @@ limiter_reconstruct_kernel(int, int, int nv, const double* __restrict__ patch, c
         for (int t = threadIdx.x; t < NsD; t += blockDim.x) {
             int r = t;
             long flat = 0, mul = 1;
-            for (int a = DIM - 1; a >= 0; a--) { flat += (long)(r % Ns + 1) * mul; mul *= S; r /= Ns; }
+            for (int a = DIM - 1; a >= 0; a--) { flat += (long)(r % Ns + H) * mul; mul *= S; r /= Ns; }
             A[t] = pt[flat * nv + v];
         }
         __syncthreads();
@@ -235,9 +238,10 @@ template <int DIM, int N> struct LimBuf {
     static size_t bytes(int nv) { return sizeof(double) * (size_t)(B1 + B2) * nv; }
 };
 
-// out(t, acc[NV]) for t over (outer, nr, inner);  acc[v] = sum_c M[r0 + r][c] * in((o*C + c)*inner + in_i, v)
+// out(t, acc[NV]) for t over (outer, nr, inner);  acc[v] = sum_c M[r0 + rstep r][c] * in((o*C + c)*inner + in_i, v)
+// rstep = -1: the rows in descending order (a mirror image across a domain face); same sums, same order
 template <int C, int NV, class In, class Out>
-__device__ inline void lim_apply_v(const double* M, int ldm, int r0, int nr, int dim, const int* e, int axis, In in, Out out) {
+__device__ inline void lim_apply_v(const double* M, int ldm, int r0, int nr, int dim, const int* e, int axis, In in, Out out, int rstep = 1) {
     unsigned inner = 1, outer = 1;
     for (int a = axis + 1; a < dim; a++) inner *= e[a];
     for (int a = 0; a < axis; a++) outer *= e[a];
@@ -245,7 +249,7 @@ __device__ inline void lim_apply_v(const double* M, int ldm, int r0, int nr, int
     for (unsigned t = threadIdx.x; t < total; t += blockDim.x) {
         const unsigned q = t / inner, in_i = t - q * inner;
         const unsigned o = q / (unsigned)nr, r = q - o * nr;
-        const double* mr = M + (r0 + r) * ldm;
+        const double* mr = M + (r0 + rstep * (int)r) * ldm;
         double acc[NV];
 #pragma unroll
         for (int v = 0; v < NV; v++) acc[v] = 0.0;
@@ -382,14 +386,14 @@ limiter_project_all_kernel(long nc0, long nc1, long nc2, const double* __restric
         }
 }
 
-template <int DIM, int N, int NV>
+template <int DIM, int N, int NV, int H = 1>
 __global__ void __launch_bounds__((LimBuf<DIM, N>::NT_R))
 limiter_reconstruct_all_kernel(const double* __restrict__ patch, const long* __restrict__ cells, double* __restrict__ u,
                                const double* __restrict__ R_global) {
     extern __shared__ __attribute__((aligned(16))) double lim_sm[];
     const double* R = R_global;
     using LB = LimBuf<DIM, N>;
-    constexpr int Ns = LB::Ns, S = Ns + 2, NN = LB::NN;
+    constexpr int Ns = LB::Ns, S = Ns + 2 * H, NN = LB::NN;
     constexpr int SS = DIM == 3 ? S * S * S : S * S;
     double* X = lim_sm;                                            // N_s^2 N (3-D) | N_s N (2-D): after one pass
     double* Y = lim_sm + (size_t)LB::B1 * NV;                      // N_s N^2: after two
@@ -404,7 +408,7 @@ limiter_reconstruct_all_kernel(const double* __restrict__ patch, const long* __r
         unsigned r = i;
         long flat = 0, mul = 1;
 #pragma unroll
-        for (int a = DIM - 1; a >= 0; a--) { flat += (long)(r % Ns + 1) * mul; mul *= S; r /= Ns; }
+        for (int a = DIM - 1; a >= 0; a--) { flat += (long)(r % Ns + H) * mul; mul *= S; r /= Ns; }
         return pt[flat * NV + v];
     };
     auto fromX = [&](unsigned i, int v) { return X[i * NV + v]; };
@@ -435,8 +439,222 @@ limiter_reconstruct_all_kernel(const double* __restrict__ patch, const long* __r
     }
 }
 
+// ------------------------------------------------------------------------------------------------------------------
+// Patches with halo 2 for the second-order patch update (EXA_FV_MUSCL_HANCOCK).  The patch [(N_s+4)^DIM][nv] is the
+// window of the ghost-extended global subcell array (the projected block, extended by two layers axis by axis, in axis order, over the
+// full transverse range -- solvers.fill_halos_boundary):
+//   interior                        (P x .. x P) u of the cell
+//   face halos, two layers          the two adjacent subcell layers of the face neighbour's projection (normal axis first, two rows of P)
+//   edge entries at depth (1, 1)    from the diagonal cell c +- e_a +- e_b: both normal axes first, one row of P each (4 points in 2-D,
+//                                   12 lines in 3-D; one cell load and O(N^2 nv) FMAs each)
+//   everything else in the halo     nearest interior value (depth 2 x halo, 3-D corners: never read by the update)
+// Domain faces: kind[a*2+side] (FV_FACE_*) and data[a*2+side][nv].  Across a MIRROR face the source cell stays, the subcell rows along
+// that axis come in mirrored order (lim_apply_v's row step -1) and the value is multiplied by the face's signs; across a STATE face the
+// value is the face's state.  The rules of two axes compose in axis order, the later axis last: STATE on the later axis wins, a mirror
+// on the later axis multiplies what the earlier axis gave (its state included).
+// One form for every variable count: a lane carries NV variables of an output element, the nv variables go in nv / NV rounds
+// (NV = nv = 5: one round, every access a contiguous AoS run, as limiter_project_all_kernel; NV = 1: the strides of the per-variable kernels).
+// LDS: the two buffers of LimBuf -- two normal rows instead of one only enlarge the small intermediates (2 N^2 <= N_s N^2).
+// ------------------------------------------------------------------------------------------------------------------
+struct LimFaces {
+    int kind[6];
+    const double* data;
+};
+
+template <int DIM, int N, int NV>
+__global__ void __launch_bounds__((LimBuf<DIM, N>::NT))
+limiter_project_halo2_kernel(int nv, long nc0, long nc1, long nc2, const double* __restrict__ u, const long* __restrict__ cells,
+                             double* __restrict__ patch, const double* __restrict__ P_global, LimFaces fk) {
+    extern __shared__ __attribute__((aligned(16))) double lim_sm[];
+    using LB = LimBuf<DIM, N>;
+    constexpr int Ns = LB::Ns, S = Ns + 4, NN = LB::NN;
+    constexpr int SS = DIM == 3 ? S * S * S : S * S, LAYER = DIM == 3 ? Ns * Ns : Ns;
+    double* X = lim_sm;
+    double* Y = lim_sm + (size_t)LB::B1 * NV;
+    __shared__ double Psh[Ns * N];
+    const long cell = cells[blockIdx.x];
+    if (cell < 0) return;                                          // empty slot of a capacity-sized cell list
+    for (int t = threadIdx.x; t < Ns * N; t += blockDim.x) Psh[t] = P_global[t];
+    const double* P = Psh;                                         // (visible after the barrier behind the first load of u)
+    double* pt = patch + (long)blockIdx.x * SS * nv;
+    const long nc[3] = {nc0, nc1, nc2};
+    long cc[3];
+    { long b = cell; cc[2] = DIM == 3 ? b % nc2 : 0; if (DIM == 3) b /= nc2; cc[1] = b % nc1; cc[0] = b / nc1; }
+    auto fromX = [&](unsigned i, int v) { return X[i * NV + v]; };
+    auto fromY = [&](unsigned i, int v) { return Y[i * NV + v]; };
+    auto toX = [&](unsigned t, const double (&a)[NV]) {
+#pragma unroll
+        for (int v = 0; v < NV; v++) X[t * NV + v] = a[v];
+    };
+    auto toY = [&](unsigned t, const double (&a)[NV]) {
+#pragma unroll
+        for (int v = 0; v < NV; v++) Y[t * NV + v] = a[v];
+    };
+    // what lies across face (a, side) of THIS cell: the face's kind at the domain face, the periodic wrap / the neighbour cell elsewhere
+    auto kind_of = [&](int a, int side) { return cc[a] == (side ? nc[a] - 1 : 0) ? fk.kind[a * 2 + side] : FV_FACE_PERIODIC; };
+    for (int v0 = 0; v0 < nv; v0 += NV) {
+        auto load_cell = [&](long c) {                             // X <- the NV variables of cell c (NV == nv: one contiguous run)
+            __syncthreads();                                       // X and Y are free (the previous product has written its result)
+            for (int t = threadIdx.x; t < NN * NV; t += blockDim.x) X[t] = u[(c * NN + t / NV) * nv + v0 + t % NV];
+            __syncthreads();
+        };
+        // ---- own projection: u -> X -> Y (-> X) -> patch interior
+        load_cell(cell);
+        {
+            int e[3] = {N, N, N};
+            lim_apply_v<N, NV>(P, N, 0, Ns, DIM, e, 0, fromX, toY);
+            e[0] = Ns;
+            __syncthreads();
+            auto to_patch = [&](unsigned t, const double (&a)[NV]) {
+                unsigned r = t;
+                long flat = 0, mul = 1;
+#pragma unroll
+                for (int ax = DIM - 1; ax >= 0; ax--) { flat += (long)(r % Ns + 2) * mul; mul *= S; r /= Ns; }
+#pragma unroll
+                for (int v = 0; v < NV; v++) pt[flat * nv + v0 + v] = a[v];
+            };
+            if constexpr (DIM == 3) {
+                lim_apply_v<N, NV>(P, N, 0, Ns, DIM, e, 1, fromY, toX);
+                e[1] = Ns;
+                __syncthreads();
+                lim_apply_v<N, NV>(P, N, 0, Ns, DIM, e, 2, fromX, to_patch);
+            } else {
+                lim_apply_v<N, NV>(P, N, 0, Ns, DIM, e, 1, fromY, to_patch);
+            }
+        }
+        __syncthreads();                                           // the interior is in global memory, visible to the workgroup
+        // halo entries the update never reads (a second layer together with another halo coordinate, 3-D corners): nearest interior value
+        for (int t = threadIdx.x; t < SS; t += blockDim.x) {
+            int I[3] = {0, 0, 0}, r = t, nh = 0, deep = 0;
+            for (int a = DIM - 1; a >= 0; a--) {
+                I[a] = r % S;
+                r /= S;
+                nh += (I[a] < 2 || I[a] > Ns + 1) ? 1 : 0;
+                deep += (I[a] == 0 || I[a] == S - 1) ? 1 : 0;
+            }
+            if (nh < 2 || (nh == 2 && deep == 0)) continue;        // interior, face halos, edge entries: written elsewhere
+            long flat = 0;
+            for (int a = 0; a < DIM; a++) {
+                const int ci = I[a] < 2 ? 2 : (I[a] > Ns + 1 ? Ns + 1 : I[a]);
+                flat = flat * S + ci;
+            }
+#pragma unroll
+            for (int v = 0; v < NV; v++) pt[(long)t * nv + v0 + v] = pt[flat * nv + v0 + v];
+        }
+        // ---- face halos: two layers
+        for (int a = 0; a < DIM; a++)
+            for (int side = 0; side < 2; side++) {
+                const int f = a * 2 + side, kind = kind_of(a, side);
+                const double* fd = fk.data ? fk.data + (long)f * nv + v0 : nullptr;
+                const bool mirror = kind == FV_FACE_MIRROR;
+                // t enumerates (axis 0, .., axis DIM-1) lexicographically with extent 2 along a: layer i of the halo, outwards at the high side
+                auto to_layers = [&](unsigned t, const double (&acc)[NV]) {
+                    unsigned r = t;
+                    int idx[3] = {0, 0, 0};
+                    for (int b = DIM - 1; b >= 0; b--) {
+                        const unsigned ext = b == a ? 2 : Ns;
+                        const int i = r % ext;
+                        r /= ext;
+                        idx[b] = b == a ? (side ? Ns + 2 + i : i) : i + 2;
+                    }
+                    long flat = 0;
+                    for (int b = 0; b < DIM; b++) flat = flat * S + idx[b];
+#pragma unroll
+                    for (int v = 0; v < NV; v++) pt[flat * nv + v0 + v] = mirror ? acc[v] * fd[v] : acc[v];
+                };
+                if (kind == FV_FACE_STATE) {
+                    for (int t = threadIdx.x; t < 2 * LAYER; t += blockDim.x) {
+                        double acc[NV];
+#pragma unroll
+                        for (int v = 0; v < NV; v++) acc[v] = fd[v];
+                        to_layers(t, acc);
+                    }
+                    continue;
+                }
+                long nb[3] = {cc[0], cc[1], cc[2]};
+                if (!mirror) nb[a] = (nb[a] + (side ? 1 : nc[a] - 1)) % nc[a];
+                load_cell((nb[0] * nc1 + nb[1]) * (DIM == 3 ? nc2 : 1) + nb[2]);
+                // rows of the source along a for the layers i = 0, 1: wrap low Ns-2, Ns-1; wrap high 0, 1; mirror low 1, 0; mirror high Ns-1, Ns-2
+                const int r0 = mirror ? (side ? Ns - 1 : 1) : (side ? 0 : Ns - 2), rstep = mirror ? -1 : 1;
+                int e2[3] = {N, N, N};
+                const int b0 = a, b1 = (a + 1) % DIM, b2 = (a + 2) % DIM;
+                lim_apply_v<N, NV>(P, N, r0, 2, DIM, e2, b0, fromX, toY, rstep);              // normal axis first: the two adjacent layers only
+                e2[b0] = 2;
+                __syncthreads();
+                if constexpr (DIM == 3) {
+                    lim_apply_v<N, NV>(P, N, 0, Ns, DIM, e2, b1, fromY, toX);
+                    e2[b1] = Ns;
+                    __syncthreads();
+                    lim_apply_v<N, NV>(P, N, 0, Ns, DIM, e2, b2, fromX, to_layers);
+                } else {
+                    lim_apply_v<N, NV>(P, N, 0, Ns, DIM, e2, b1, fromY, to_layers);
+                }
+            }
+        // ---- edge entries: first halo layer along a and b (a < b), the whole line along the third axis
+        for (int a = 0; a < DIM; a++)
+            for (int b = a + 1; b < DIM; b++)
+                for (int sides = 0; sides < 4; sides++) {
+                    const int sa = sides >> 1, sb = sides & 1;
+                    const int ka = kind_of(a, sa), kb = kind_of(b, sb);
+                    const double* da = fk.data ? fk.data + (long)(a * 2 + sa) * nv + v0 : nullptr;
+                    const double* db = fk.data ? fk.data + (long)(b * 2 + sb) * nv + v0 : nullptr;
+                    const int c3 = DIM == 3 ? 3 - a - b : -1;      // the axis the line runs along
+                    auto to_line = [&](unsigned t, const double (&acc)[NV]) {
+                        int idx[3] = {0, 0, 0};
+                        idx[a] = sa ? Ns + 2 : 1;
+                        idx[b] = sb ? Ns + 2 : 1;
+                        if (DIM == 3) idx[c3] = (int)t + 2;
+                        long flat = 0;
+                        for (int x = 0; x < DIM; x++) flat = flat * S + idx[x];
+#pragma unroll
+                        for (int v = 0; v < NV; v++) pt[flat * nv + v0 + v] = acc[v];
+                    };
+                    if (kb == FV_FACE_STATE || ka == FV_FACE_STATE) {
+                        // the later axis is applied last: its state wins; its mirror multiplies the earlier axis's state
+                        for (int t = threadIdx.x; t < (DIM == 3 ? Ns : 1); t += blockDim.x) {
+                            double acc[NV];
+#pragma unroll
+                            for (int v = 0; v < NV; v++) acc[v] = kb == FV_FACE_STATE ? db[v] : (kb == FV_FACE_MIRROR ? da[v] * db[v] : da[v]);
+                            to_line(t, acc);
+                        }
+                        continue;
+                    }
+                    long nb[3] = {cc[0], cc[1], cc[2]};
+                    if (ka == FV_FACE_PERIODIC) nb[a] = (nb[a] + (sa ? 1 : nc[a] - 1)) % nc[a];
+                    if (kb == FV_FACE_PERIODIC) nb[b] = (nb[b] + (sb ? 1 : nc[b] - 1)) % nc[b];
+                    load_cell((nb[0] * nc1 + nb[1]) * (DIM == 3 ? nc2 : 1) + nb[2]);
+                    // the one row next to the face: the neighbour's nearest (wrap) or the cell's own nearest (mirror)
+                    const int ra = (ka == FV_FACE_MIRROR) == (sa == 1) ? Ns - 1 : 0;
+                    const int rb = (kb == FV_FACE_MIRROR) == (sb == 1) ? Ns - 1 : 0;
+                    auto to_line_signed = [&](unsigned t, const double (&acc)[NV]) {
+                        double sg[NV];
+#pragma unroll
+                        for (int v = 0; v < NV; v++) {
+                            sg[v] = acc[v];
+                            if (ka == FV_FACE_MIRROR) sg[v] *= da[v];
+                            if (kb == FV_FACE_MIRROR) sg[v] *= db[v];
+                        }
+                        to_line(t, sg);
+                    };
+                    int e2[3] = {N, N, N};
+                    lim_apply_v<N, NV>(P, N, ra, 1, DIM, e2, a, fromX, toY);
+                    e2[a] = 1;
+                    __syncthreads();
+                    if constexpr (DIM == 3) {
+                        lim_apply_v<N, NV>(P, N, rb, 1, DIM, e2, b, fromY, toX);
+                        e2[b] = 1;
+                        __syncthreads();
+                        lim_apply_v<N, NV>(P, N, 0, Ns, DIM, e2, c3, fromX, to_line_signed);
+                    } else {
+                        lim_apply_v<N, NV>(P, N, rb, 1, DIM, e2, b, fromY, to_line_signed);
+                    }
+                }
+    }
+}
+
 // launch of the all-variables kernels (NV = 5: the Euler-sized systems of the configs); false: not built / does not fit -> per-variable path
-template <int DIM, int N, int NV, int NT, class K, class... Args>
+// TAG tells apart kernels of one signature (the static flag below is per instantiation)
+template <int DIM, int N, int NV, int NT, int TAG = 0, class K, class... Args>
 static bool lim_launch_all(K kern, long n, hipStream_t s, Args... args) {
     const size_t bytes = LimBuf<DIM, N>::bytes(NV);
     if (bytes + 2048 > 160 * 1024) return false;                   // (+ the operator copy and alignment)
@@ -519,8 +737,10 @@ int limiter_face_layers(int dim, int N, int Ns, int nv, const long* nc, const do
     return 0;
 }
 
-int limiter_reconstruct(int dim, int N, int Ns, int nv, const double* patch, const long* cells, long n, double* u,
-                        const double* Rdev, hipStream_t s) {
+// H: halo layers of the patches (1: the first-order update's, 2: the second-order update's); the interior is read at offset H
+template <int H>
+static int lim_reconstruct_h(int dim, int N, int Ns, int nv, const double* patch, const long* cells, long n, double* u,
+                             const double* Rdev, hipStream_t s) {
     if (n <= 0) return 0;
 #ifndef EXA_LIM_PER_VARIABLE
     if (nv == 5 && !lim_per_variable()) {
@@ -528,8 +748,8 @@ int limiter_reconstruct(int dim, int N, int Ns, int nv, const double* patch, con
         switch (N) {
 #define X(NN_)                                                                                                                         \
         case NN_:                                                                                                                      \
-            done = dim == 2 ? lim_launch_all<2, NN_, 5, LimBuf<2, NN_>::NT_R>(limiter_reconstruct_all_kernel<2, NN_, 5>, n, s, patch, cells, u, Rdev)        \
-                            : lim_launch_all<3, NN_, 5, LimBuf<3, NN_>::NT_R>(limiter_reconstruct_all_kernel<3, NN_, 5>, n, s, patch, cells, u, Rdev);       \
+            done = dim == 2 ? lim_launch_all<2, NN_, 5, LimBuf<2, NN_>::NT_R, H>(limiter_reconstruct_all_kernel<2, NN_, 5, H>, n, s, patch, cells, u, Rdev)        \
+                            : lim_launch_all<3, NN_, 5, LimBuf<3, NN_>::NT_R, H>(limiter_reconstruct_all_kernel<3, NN_, 5, H>, n, s, patch, cells, u, Rdev);       \
             break;
             EXA_LIM_CASES(X)
 #undef X
@@ -545,8 +765,8 @@ int limiter_reconstruct(int dim, int N, int Ns, int nv, const double* patch, con
     switch (N) {
 #define X(NN_)                                                                                                                         \
     case NN_:                                                                                                                          \
-        if (dim == 2) hipLaunchKernelGGL((limiter_reconstruct_kernel<2, NN_>), dim3((unsigned)n), dim3(256), 0, s, N, Ns, nv, patch, cells, u, Rdev); \
-        else hipLaunchKernelGGL((limiter_reconstruct_kernel<3, NN_>), dim3((unsigned)n), dim3(256), 0, s, N, Ns, nv, patch, cells, u, Rdev);      \
+        if (dim == 2) hipLaunchKernelGGL((limiter_reconstruct_kernel<2, NN_, H>), dim3((unsigned)n), dim3(256), 0, s, N, Ns, nv, patch, cells, u, Rdev); \
+        else hipLaunchKernelGGL((limiter_reconstruct_kernel<3, NN_, H>), dim3((unsigned)n), dim3(256), 0, s, N, Ns, nv, patch, cells, u, Rdev);      \
         break;
         EXA_LIM_CASES(X)
 #undef X
@@ -554,6 +774,59 @@ int limiter_reconstruct(int dim, int N, int Ns, int nv, const double* patch, con
     }
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) { set_error("limiter_reconstruct launch: %s", hipGetErrorString(e)); return -2; }
+    return 0;
+}
+
+int limiter_reconstruct(int dim, int N, int Ns, int nv, const double* patch, const long* cells, long n, double* u,
+                        const double* Rdev, hipStream_t s) {
+    return lim_reconstruct_h<1>(dim, N, Ns, nv, patch, cells, n, u, Rdev, s);
+}
+
+int limiter_reconstruct_halo(int dim, int N, int Ns, int nv, const double* patch, const long* cells, long n, double* u,
+                             const double* Rdev, int halo, hipStream_t s) {
+    return halo == 2 ? lim_reconstruct_h<2>(dim, N, Ns, nv, patch, cells, n, u, Rdev, s)
+                     : lim_reconstruct_h<1>(dim, N, Ns, nv, patch, cells, n, u, Rdev, s);
+}
+
+// kinds: FV_FACE_* of the 2 dim domain faces (null: all periodic); data: device, [2 dim][nv] (signs of a mirror face, state of a state face)
+int limiter_project_halo2(int dim, int N, int nv, const long* nc, const double* u, const long* cells, long n, double* patch,
+                          const double* Pdev, const int* kinds, const double* data, hipStream_t s) {
+    if (n <= 0) return 0;
+    LimFaces fk{};
+    for (int f = 0; f < 6; f++) fk.kind[f] = (kinds && f < 2 * dim) ? kinds[f] : FV_FACE_PERIODIC;
+    fk.data = data;
+    const long nc2 = dim == 3 ? nc[2] : 1L;
+    bool done = false;
+    // five variables at a time where that divides the count and fits the LDS, else one at a time: the same kernel
+#ifndef EXA_LIM_PER_VARIABLE
+    if (nv % 5 == 0 && !lim_per_variable()) {
+        switch (N) {
+#define X(NN_)                                                                                                                         \
+        case NN_:                                                                                                                      \
+            done = dim == 2 ? lim_launch_all<2, NN_, 5, LimBuf<2, NN_>::NT>(limiter_project_halo2_kernel<2, NN_, 5>, n, s, nv, nc[0], nc[1], nc2, u, cells, patch, Pdev, fk) \
+                            : lim_launch_all<3, NN_, 5, LimBuf<3, NN_>::NT>(limiter_project_halo2_kernel<3, NN_, 5>, n, s, nv, nc[0], nc[1], nc2, u, cells, patch, Pdev, fk); \
+            break;
+            EXA_LIM_CASES(X)
+#undef X
+        default: break;
+        }
+    }
+#endif
+    if (!done) {
+        switch (N) {
+#define X(NN_)                                                                                                                         \
+        case NN_:                                                                                                                      \
+            done = dim == 2 ? lim_launch_all<2, NN_, 1, LimBuf<2, NN_>::NT>(limiter_project_halo2_kernel<2, NN_, 1>, n, s, nv, nc[0], nc[1], nc2, u, cells, patch, Pdev, fk) \
+                            : lim_launch_all<3, NN_, 1, LimBuf<3, NN_>::NT>(limiter_project_halo2_kernel<3, NN_, 1>, n, s, nv, nc[0], nc[1], nc2, u, cells, patch, Pdev, fk); \
+            break;
+            EXA_LIM_CASES(X)
+#undef X
+        default: set_error("limiter: N = %d is not built", N); return -1;
+        }
+    }
+    if (!done) { set_error("limiter_project_halo2: the kernel's LDS attribute could not be set"); return -2; }
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) { set_error("limiter_project_halo2 launch: %s", hipGetErrorString(e)); return -2; }
     return 0;
 }
 

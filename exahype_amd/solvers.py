@@ -14,7 +14,8 @@ import os
 import numpy as np
 
 from . import _lib
-from ._lib import (FV_FAITHFUL, FV_MUSCL_HANCOCK, FV_RUSANOV, PDE_ADVECTION, PDE_EULER, PDE_EULER_REF2D, check, darr, larr)
+from ._lib import (FV_FAITHFUL, FV_MUSCL_HANCOCK, FV_RUSANOV, PDE_ADVECTION, PDE_EULER, PDE_EULER_REF2D, PDE_FLAG_MUSCL_HANCOCK, PDE_FLAG_NCP, PDE_FLAG_XT,
+                   check, darr, larr)
 from .boundary import Dirichlet, Outflow, Wall, coefficients as _bc_coefficients, fv_faces as _fv_faces, validate_boundary
 
 
@@ -1098,12 +1099,23 @@ class SubcellLimiter:
 
     At a domain face with a boundary condition (AderDgSolver(boundary=...)) the ghost subcell layer is the boundary cell's own adjacent
     layer (exa_lim_face_layers), unchanged for Outflow, times the sign for a Wall, and the prescribed state at the ghost subcells' centres
-    at the step's start time for Dirichlet; the DMP neighbourhood of detect() does not reach across such a face."""
+    at the step's start time for Dirichlet; the DMP neighbourhood of detect() does not reach across such a face.
+
+    fv_mode=FV_MUSCL_HANCOCK: the troubled cells of step, step_a_posteriori and run take the SECOND-order patch update (patch_size 2p+1, halo 2:
+    face halos two layers deep and the edge entries of the diagonal cells, exa_lim_project_patches_halo2); see __init__ for what that mode serves."""
 
     DEFAULT_FRACTION = 0.1          # default capacity: this share of the block's cells (at least 16)
 
-    def __init__(self, solver, capacity=None):
-        """capacity: upper bound of the number of troubled cells per step; the FV patch array [capacity][(N_s+2)^dim][n_vars]
+    def __init__(self, solver, capacity=None, fv_mode=FV_RUSANOV):
+        """fv_mode: the patch update of the troubled cells.  FV_RUSANOV (default): first order, patches with halo 1.  FV_MUSCL_HANCOCK: the
+        second-order update (FVRusanovKernel) on patches with halo 2 -- face halos two layers deep and the edge entries from the diagonal
+        cells (exa_lim_project_patches_halo2); the domain faces' conditions enter the projection as mirror / state faces (Outflow: a mirror
+        with signs 1; Wall: a mirror with its signs; a constant Dirichlet: its state).  That mode serves one block, constant Dirichlet
+        states, term sets the second-order update serves (built-in Euler / advection, SympyPDE(muscl_hancock=True)) and patches whose
+        LDS plan fits a compute unit (five variables: every 2-D order, 3-D N <= 5); anything else raises ValueError here.  Not together
+        with conservative=True.
+
+        capacity: upper bound of the number of troubled cells per step; the FV patch array [capacity][(N_s+2)^dim][n_vars]
         is allocated once (196 KB per patch at p = 7) and the glue kernels launch `capacity` workgroups per step, so the
         default is a bounded share of the block -- max(16, 10 % of its cells) -- not the whole block (262 144 cells at p = 7
         would be 51 GB).  A step with more troubled cells than that is reported by check(): construct the limiter again with a
@@ -1114,11 +1126,20 @@ class SubcellLimiter:
         self.s = solver
         self.exchange_events = None       # measurement hook (bench.py): one (start, end) event pair per step around the limiter's own two exchanges
         self.Ns = 2 * solver.N - 1
-        self.patch_doubles = solver.lib.exa_lim_patch_count(solver._plan)
+        if fv_mode not in (FV_RUSANOV, FV_MUSCL_HANCOCK):
+            raise ValueError("SubcellLimiter: fv_mode must be FV_RUSANOV or FV_MUSCL_HANCOCK, got %r" % (fv_mode,))
+        self.fv_mode = fv_mode
+        self.fv_halo = 2 if fv_mode == FV_MUSCL_HANCOCK else 1
+        if fv_mode == FV_MUSCL_HANCOCK:
+            self._muscl_refusals()
+            self.patch_doubles = solver.lib.exa_lim_patch_count_halo(solver._plan, 2)
+        else:
+            self.patch_doubles = solver.lib.exa_lim_patch_count(solver._plan)
         ncell = int(np.prod(solver.nc))
         if capacity is None:
             capacity = max(16, int(self.DEFAULT_FRACTION * ncell))
         self.capacity = max(1, min(int(capacity), ncell))
+        self._fv = self._muscl_plan() if fv_mode == FV_MUSCL_HANCOCK else None     # (a shape the plan refuses: before anything is allocated)
         need = self.capacity * self.patch_doubles * 8
         free = torch.cuda.mem_get_info(solver.dev)[0]
         if need > free:
@@ -1127,8 +1148,9 @@ class SubcellLimiter:
         self._patches = torch.empty((self.capacity, self.patch_doubles), dtype=torch.float64, device=solver.dev)
         self._cells = torch.full((self.capacity + 1,), -1, dtype=torch.int64, device=solver.dev)     # + dump slot
         self._arange = torch.arange(ncell, dtype=torch.int64, device=solver.dev)
-        self._fv = FVRusanovKernel(solver.dim, self.Ns, 1, solver.nv, 0, self.capacity, pde=solver.pde, mode=FV_RUSANOV,
-                                   device=solver.dev.index or 0)
+        if self._fv is None:
+            self._fv = FVRusanovKernel(solver.dim, self.Ns, 1, solver.nv, 0, self.capacity, pde=solver.pde, mode=FV_RUSANOV,
+                                       device=solver.dev.index or 0)
         self.overflow = torch.zeros((), dtype=torch.bool, device=solver.dev)
         self._ovf_host = torch.zeros(1, dtype=torch.uint8).pin_memory()
         self._ovf_event = torch.cuda.Event()
@@ -1139,13 +1161,51 @@ class SubcellLimiter:
         self._bc_layers = {}              # (d, side) -> ghost subcell layer [transverse cells][Ns^(dim-1)][n_vars] of a domain face
         for d, side, _, _, _ in solver._bc:
             nt = ncell // solver.nc[d]
-            self._bc_layers[(d, side)] = torch.zeros((nt, self.Ns ** (solver.dim - 1), solver.nv), dtype=torch.float64, device=solver.dev)
+            # (halo 2: the faces' conditions enter the projection itself -- the keys alone say which faces have no neighbour)
+            self._bc_layers[(d, side)] = None if self.fv_halo == 2 else torch.zeros((nt, self.Ns ** (solver.dim - 1), solver.nv), dtype=torch.float64, device=solver.dev)
         if solver.halo is not None:
             stage = solver.halo.stage
             self.hx_mask = HaloExchange(solver.part, solver.nc, 1, solver.dev, stage_through_host=stage)
             self.hx_layer = HaloExchange(solver.part, solver.nc, self.Ns ** (solver.dim - 1) * solver.nv, solver.dev,
                                          stage_through_host=stage)
         self._face_kind = self._face_kinds()
+        self._fv_face_kind = self._fv_face_data = None
+        if fv_mode == FV_MUSCL_HANCOCK and solver._bc:
+            # what lies across the domain faces, for the halo-2 projection: the kinds and data of exa_fv_grid_step_device_bc
+            kinds, data, _ = _fv_faces(solver.boundary, solver.dim, solver.nv, 0, solver.pde)
+            self._fv_face_kind = (C.c_int * len(kinds))(*kinds)
+            self._fv_face_data = torch.as_tensor(data, dtype=torch.float64).to(solver.dev)
+
+    def _muscl_refusals(self):
+        """What fv_mode=FV_MUSCL_HANCOCK does not serve: each a ValueError that names the way out."""
+        s = self.s
+        who = "SubcellLimiter(fv_mode=FV_MUSCL_HANCOCK)"
+        if s.halo is not None:
+            raise ValueError("%s: the grid is partitioned; the patches with halo 2 would need two subcell layers and the edge lines of diagonal "
+                             "ranks by exchange, which is not built -- run it on one block or use fv_mode=FV_RUSANOV" % who)
+        for d, side, bc, _, _ in s._bc:
+            if isinstance(bc, Dirichlet) and not bc.constant:
+                raise ValueError("%s: face (%d, %d) has a function-valued Dirichlet condition; the entries beyond a domain corner lie outside "
+                                 "any face's layer -- use a constant Dirichlet state or fv_mode=FV_RUSANOV" % (who, d, side))
+        flags = s.lib.exa_pde_flags(int(s.pde))
+        xt_ncp = flags & (PDE_FLAG_XT | PDE_FLAG_NCP)
+        if xt_ncp or (int(s.pde) >= 100 and not flags & PDE_FLAG_MUSCL_HANCOCK):
+            raise ValueError("%s: term set %d %s; generate it with SympyPDE(muscl_hancock=True) (conservative terms of the state alone: no "
+                             "position / time dependence, no non-conservative product) or use fv_mode=FV_RUSANOV"
+                             % (who, int(s.pde), "has position / time dependent terms or a non-conservative product" if xt_ncp
+                                else "does not carry the second-order patch update"))
+
+    def _muscl_plan(self):
+        """The FV plan of the second-order update for `capacity` patches with halo 2.  A shape exa_fv_plan_create refuses (the LDS plan of one
+        patch exceeds a compute unit: its message names both byte counts) is a ValueError that carries that message."""
+        s = self.s
+        try:
+            return FVRusanovKernel(s.dim, self.Ns, 2, s.nv, 0, self.capacity, pde=s.pde, mode=FV_MUSCL_HANCOCK, device=s.dev.index or 0)
+        except _lib.ExaHypeHipError as e:
+            if "bytes of LDS" not in str(e):
+                raise
+            raise ValueError("SubcellLimiter(fv_mode=FV_MUSCL_HANCOCK): order N = %d in %d-D is not served -- %s; larger patches need plane "
+                             "streaming (DESIGN.md 8 c), which is not built: use a lower order or fv_mode=FV_RUSANOV" % (s.N, s.dim, e)) from None
 
     def operators(self):
         N, Ns = self.s.N, self.Ns
@@ -1321,6 +1381,12 @@ class SubcellLimiter:
         the domain faces, projection."""
         torch = _torch()
         s = self.s
+        if self.fv_halo == 2:                                  # one block; the faces' conditions enter the projection itself
+            check(s.lib.exa_lim_project_patches_halo2(s._plan, C.c_void_p(u.data_ptr()), C.c_void_p(self._cells.data_ptr()), self.capacity,
+                                                      C.c_void_p(self._patches.data_ptr()), self._fv_face_kind,
+                                                      C.c_void_p(self._fv_face_data.data_ptr()) if self._fv_face_data is not None else None,
+                                                      _stream_ptr()))
+            return
         ghosts = None
         if self.hx_layer is not None:                          # every rank takes part, troubled cells or not
             nc3 = s.nc + [1] * (3 - s.dim)
@@ -1350,6 +1416,10 @@ class SubcellLimiter:
             self._fv.time_step(patches.reshape(-1), dt, s.dx[0] / self.Ns, slot=cells, t=t0, centres=cen)
         else:
             self._fv.time_step(patches.reshape(-1), dt, s.dx[0] / self.Ns, slot=cells)
+        if self.fv_halo == 2:
+            check(s.lib.exa_lim_reconstruct_patches_halo(s._plan, C.c_void_p(patches.data_ptr()), C.c_void_p(cells.data_ptr()), cap,
+                                                         C.c_void_p(s.u.data_ptr()), 2, _stream_ptr()))
+            return
         check(s.lib.exa_dg_reconstruct_patches(s._plan, C.c_void_p(patches.data_ptr()), C.c_void_p(cells.data_ptr()), cap,
                                                C.c_void_p(s.u.data_ptr()), _stream_ptr()))
 
@@ -1373,6 +1443,10 @@ class SubcellLimiter:
         s = self.s
         if self._fvflux is not None:
             return
+        if self.fv_mode == FV_MUSCL_HANCOCK:
+            raise ValueError("SubcellLimiter.%s(conservative=True): not with fv_mode=FV_MUSCL_HANCOCK -- exa_lim_face_flux is the first-order flux "
+                             "between boundary layer and halo layer, not the flux the second-order update applies, so the totals would drift; "
+                             "use fv_mode=FV_RUSANOV for the conservative interface" % who)
         if s.halo is not None:
             raise ValueError("SubcellLimiter.%s(conservative=True): the grid is partitioned; the exchange of the FV face fluxes between the "
                              "blocks of a sharded grid is out of scope of the conservative interface (run it on one block)" % who)

@@ -312,6 +312,30 @@ int exa_lim_face_layers(exa_dg_plan* plan, const double* u_dev, int d, int side,
                         void* stream);
 int exa_dg_project_patches_ghost(exa_dg_plan* plan, const double* u_dev, const long* cells_dev, long n, double* patch_dev,
                                  const double* const* ghost_layers_dev, void* stream);
+/* Patches with halo 2, what the second-order patch update (EXA_FV_MUSCL_HANCOCK) reads: patch_dev[n][(N_s+4)^dim][n_vars]
+ * (exa_lim_patch_count_halo(plan, 2) doubles per patch; halo 1 gives exa_lim_patch_count; EXA_ERR_INVALID for a NULL plan or another halo).
+ * The patch is the window of the ghost-extended global subcell array -- the projected block, extended by two layers axis by axis, in axis
+ * order, over the full transverse range:
+ *   interior                      the projected cell
+ *   face halos, two layers        the two adjacent subcell layers of the projected face neighbour
+ *   edge entries                  both halo coordinates in the first layer, along the whole edge (4 points in 2-D, 12 lines in 3-D): from the
+ *                                 projection of the diagonal cell c +- e_a +- e_b
+ *   everything else in the halo   (a second layer together with another halo coordinate, the 3-D corners) the nearest interior value: the
+ *                                 update never reads it
+ * face_kind[axis * 2 + side] (host, 2 dim entries of EXA_FV_FACE_*; NULL: every face periodic) and face_data_dev[(axis * 2 + side) * n_vars ..]
+ * (device; may be NULL if every face is periodic) say what lies across a face of the block, as for exa_fv_grid_step_device_bc: across an
+ * EXA_FV_FACE_MIRROR face the cell itself, its subcell rows along that axis in mirrored order (halo layer 1 takes the subcell at the face, layer 2
+ * the next one), every variable times its sign (the data); across an EXA_FV_FACE_STATE face the prescribed state (the data).  Where an entry lies
+ * across faces of two axes the rules compose in axis order, the later axis last: a state of the later axis wins, a mirror of the later axis
+ * multiplies what the earlier axis gave (a wall-wall corner: the cell's own corner subcell times both signs).  The mirror products are exact.
+ * One block only: no ghost layers of neighbour blocks.  cells_dev[i] < 0: patch i is not written.
+ * exa_lim_reconstruct_patches_halo: exa_dg_reconstruct_patches for patches with `halo` (1 | 2) layers -- the interior is read at offset halo;
+ * halo 1 is exa_dg_reconstruct_patches itself. */
+long exa_lim_patch_count_halo(const exa_dg_plan* plan, int halo);
+int exa_lim_project_patches_halo2(exa_dg_plan* plan, const double* u_dev, const long* cells_dev, long n, double* patch_dev, const int* face_kind,
+                                  const double* face_data_dev, void* stream);
+int exa_lim_reconstruct_patches_halo(exa_dg_plan* plan, const double* patch_dev, const long* cells_dev, long n, double* u_dev, int halo,
+                                     void* stream);
 /* A-posteriori (MOOD) troubled-cell detection for the limiter: the DG candidate of a step is checked AFTER the step against the
  * state it started from, and the troubled cells are redone with the FV patch update from that state.  Euler variable layout:
  * density first, energy last, min(3, n_vars - 2) momenta behind the density, gamma = 1.4.  Both are one pass over u.
