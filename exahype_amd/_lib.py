@@ -34,6 +34,7 @@ SIGNATURES = {
     "exa_fv_qout_count": (C.c_long, [_vp]),
     "exa_fv_grid_step_device": (C.c_int, [_vp, _vp, _vp, _lp, _vp, _vp, C.c_double, C.c_double, C.c_double, _vp, _vp]),
     "exa_fv_grid_step_device_bc": (C.c_int, [_vp, _vp, _vp, _lp, C.POINTER(C.c_int), _vp, _vp, C.c_double, C.c_double, C.c_double, _vp, _vp]),
+    "exa_fv_grid_step_muscl_device": (C.c_int, [_vp, _vp, _vp, _lp, C.POINTER(C.c_int), _vp, C.c_double, C.c_double, _vp, _vp]),
     "exa_fv_max_eigenvalue": (C.c_int, [_vp, _vp, C.c_int, _vp, C.c_double, C.c_double, _vp, _vp]),
     "exa_fv_time_step_device_masked": (C.c_int, [_vp, _vp, _vp, C.c_double, C.c_double, _vp]),
     "exa_fv_time_step_device_masked_at": (C.c_int, [_vp, _vp, _vp, _vp, C.c_double, C.c_double, C.c_double, _vp]),

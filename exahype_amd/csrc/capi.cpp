@@ -54,6 +54,8 @@ struct UserPde {
                     const double*, const double*, const double*, void*);
     // the term set's instantiation of the MUSCL-Hancock patch update (EXA_PDE_FLAG_MUSCL_HANCOCK; fv_muscl_user.hip)
     int (*fvm)(int, int, int, int, int, long, double*, double, double, const long*, void*, double*);
+    // ... and of its grid step on halo-less arrays (exa_user_fv_muscl_grid_launch); null in a library built before that entry existed
+    int (*fvmg)(int, int, int, int, long, const double*, double*, double, double, const void*, void*);
 };
 static std::vector<UserPde> g_user;
 
@@ -66,6 +68,15 @@ int user_fv_muscl_launch(int pde, int dim, int P, int H, int n_real, int n_aux, 
                          hipStream_t s, double* out) {
     if (pde - 100 >= (int)g_user.size() || !g_user[pde - 100].fvm) { set_error("pde %d carries no MUSCL-Hancock kernel", pde); return -1; }
     return g_user[pde - 100].fvm(dim, P, H, n_real, n_aux, n_patches, Q, dt, h, slot, (void*)s, out);
+}
+int user_fv_muscl_grid_launch(int pde, int dim, int P, int n_real, int n_aux, long n_patches, const double* Q, double* out, double dt, double h,
+                              const FvMusclGrid* grid, hipStream_t s) {
+    if (pde - 100 >= (int)g_user.size() || !g_user[pde - 100].fvmg) {
+        set_error("pde %d: its side library exports no exa_user_fv_muscl_grid_launch (built before the MUSCL-Hancock grid step existed); rebuild the "
+                  "term set (SympyPDE(..., muscl_hancock=True).build(force=True)) or use the two-pass form on the array with halo", pde);
+        return -1;
+    }
+    return g_user[pde - 100].fvmg(dim, P, n_real, n_aux, n_patches, Q, out, dt, h, grid, (void*)s);
 }
 int user_fv_maxeig(int pde, int dim, int P, int H, int n_real, int n_aux, long n_patches, const double* Q, double* lam, hipStream_t s,
                    const double* centre, double t, double h) {
@@ -181,6 +192,7 @@ int exa_register_pde(const char* library_path, int* pde_id) {
             set_error("%s asks for the MUSCL-Hancock patch update but exports no exa_user_fv_muscl_launch", library_path);
             return EXA_ERR_INVALID;
         }
+        u.fvmg = (decltype(u.fvmg))dlsym(h, "exa_user_fv_muscl_grid_launch");      // (optional: older cached builds have none)
     }
     g_user.push_back(u);
     *pde_id = 100 + (int)g_user.size() - 1;
@@ -363,6 +375,47 @@ int exa_fv_grid_step_device(exa_fv_plan* p, const double* Q_dev, double* QNext_d
     static const int all_state[6] = {EXA_FV_FACE_STATE, EXA_FV_FACE_STATE, EXA_FV_FACE_STATE, EXA_FV_FACE_STATE, EXA_FV_FACE_STATE, EXA_FV_FACE_STATE};
     return fv_grid_step("exa_fv_grid_step_device", p, Q_dev, QNext_dev, grid, boundary_dev ? all_state : nullptr, boundary_dev, centre_dev, t, dt, h, lambda_next_dev,
                                       stream);
+}
+
+int exa_fv_grid_step_muscl_device(exa_fv_plan* p, const double* Q_dev, double* QNext_dev, const long* grid, const int* face_kind,
+                                  const double* face_data_dev, double dt, double h, double* lambda_next_dev, void* stream) {
+    const char* who = "exa_fv_grid_step_muscl_device";
+    if (!p || !grid || !Q_dev || !QNext_dev) { set_error("%s: NULL argument (plan, grid, Q_dev and QNext_dev are all needed)", who); return EXA_ERR_INVALID; }
+    if (p->mode != EXA_FV_MUSCL_HANCOCK) {
+        set_error("%s: the plan's mode is %d, this entry serves EXA_FV_MUSCL_HANCOCK plans; exa_fv_grid_step_device[_bc] is the grid step of the "
+                  "other modes", who, p->mode);
+        return EXA_ERR_INVALID;
+    }
+    if (p->P < 2) {
+        set_error("%s: patch_size %d -- the second halo layer would belong to the neighbour's neighbour; patch_size >= 2 is served here, a grid of "
+                  "smaller patches by the two-pass form (fill the halos of the array with halo and call exa_fv_time_step_device)", who, p->P);
+        return EXA_ERR_INVALID;
+    }
+    if (Q_dev == QNext_dev) { set_error("%s: the new states need an array of their own (the neighbours read the old ones): pass two arrays and swap them", who); return EXA_ERR_INVALID; }
+    if (!(h > 0.0)) { set_error("%s: EXA_FV_MUSCL_HANCOCK needs the volume size h > 0", who); return EXA_ERR_INVALID; }
+    FvMusclGrid ga{{1, 1, 1}, {0, 0, 0, 0, 0, 0}, nullptr, lambda_next_dev};
+    bool bounded = false;
+    for (int f = 0; face_kind && f < 2 * p->dim; f++) {
+        if (face_kind[f] < EXA_FV_FACE_PERIODIC || face_kind[f] > EXA_FV_FACE_MIRROR) {
+            set_error("%s: face_kind[%d] = %d is none of EXA_FV_FACE_PERIODIC / _STATE / _MIRROR", who, f, face_kind[f]);
+            return EXA_ERR_INVALID;
+        }
+        ga.bkind[f] = face_kind[f];
+        bounded = bounded || face_kind[f] != EXA_FV_FACE_PERIODIC;
+    }
+    if (bounded && !face_data_dev) { set_error("%s: a face that is not periodic needs face_data_dev (its state or its signs)", who); return EXA_ERR_INVALID; }
+    ga.bstate = bounded ? face_data_dev : nullptr;                 // (null: the kernel takes every face as periodic)
+    long n = 1;
+    for (int a = 0; a < p->dim; a++) {
+        if (grid[a] < 1 || grid[a] > 0x7fffffffL) { set_error("%s: grid[%d] = %ld", who, a, grid[a]); return EXA_ERR_INVALID; }
+        ga.g[a] = (int)grid[a];
+        n *= grid[a];
+    }
+    if (n != p->n_patches) { set_error("%s: the grid has %ld patches, the plan %ld: create the plan with n_patches = the product of grid", who, n, p->n_patches); return EXA_ERR_INVALID; }
+    if (n > 0xffffffffL) { set_error("%s: %ld patches -- a grid holds at most 2^32 - 1", who, n); return EXA_ERR_INVALID; }
+    int rc = use_device(p->device);
+    if (rc) return rc;
+    return fv_muscl_grid_launch(p->dim, p->P, p->n_real, p->n_aux, p->n_patches, p->pde, Q_dev, QNext_dev, dt, h, &ga, (hipStream_t)stream);
 }
 
 int exa_fv_max_eigenvalue(exa_fv_plan* p, const double* Q_dev, int halo_less, const double* centre_dev, double t, double h, double* lambda_dev,

@@ -17,6 +17,10 @@
 // function phase 1 ran: the same bits), takes the neighbours' delta from LDS, evaluates its 2 DIM face fluxes and stores the new state.  Both
 // sides of a face evaluate fv_muscl_face on the same two states, so the flux a volume loses is bit for bit the one its neighbour gains.  The
 // window is complete before the first store, so in place is safe; the unit is compiled without FMA contraction like the Rusanov unit.
+//
+// fv_muscl_grid_kernel (further down) is the GRID form on halo-less arrays: the same plan and the same two phases (fv_muscl_predict,
+// fv_muscl_correct -- the device functions both kernels call, so the results are bit-identical), another staging -- the window is gathered from the
+// patch, its face neighbours and its diagonal neighbours -- and the next step's CFL scan reduced from the values phase 2 stores.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -64,49 +68,23 @@ __device__ __forceinline__ void fv_muscl_face(const double (&wL)[FVM_MAXV], cons
 
 template <int DIM> __host__ __device__ constexpr int fvm_pow(int b) { return DIM == 3 ? b * b * b : b * b; }
 
-template <int DIM, class PDE, int NT>
-__global__ void __launch_bounds__(NT)
-fv_muscl_kernel(double* __restrict__ Q, double* __restrict__ out, const long* __restrict__ slot, int P, int H, int m, int V, double r,
-                long n_patches, int ppb) {
-    extern __shared__ __attribute__((aligned(16))) double fvm_lds[];
-    const int S = P + 2 * H, T = P + 4, D = P + 2, off = H - 2;
-    const int tvol = fvm_pow<DIM>(T), dvol = fvm_pow<DIM>(D), ncell = fvm_pow<DIM>(P);
-    const long svol = DIM == 3 ? (long)S * S * S : (long)S * S;
-    double* img = fvm_lds;                                        // [patch slot][T^DIM][V]
-    double* del = fvm_lds + (long)ppb * tvol * V;                 // [patch slot][(P + 2)^DIM][m]
-    const long first = (long)blockIdx.x * ppb;
-    const int np = (int)(n_patches - first < ppb ? n_patches - first : ppb);
-    const int tid = (int)threadIdx.x;
-
-    // ---- stage the windows
-    const double* src = Q + first * svol * V;
-    if (off == 0) {                                               // the window is the patch: one contiguous block
-        const int total = np * tvol * V;
-        if ((reinterpret_cast<unsigned long long>(src) & 15) == 0) {
-            const fvm_v2d* s2 = reinterpret_cast<const fvm_v2d*>(src);
-            fvm_v2d* d2 = reinterpret_cast<fvm_v2d*>(img);
-            for (int i = tid; i < total / 2; i += NT) d2[i] = s2[i];
-            if ((total & 1) && tid == 0) img[total - 1] = src[total - 1];
-        } else {
-            for (int i = tid; i < total; i += NT) img[i] = src[i];
-        }
-    } else {                                                      // H > 2: rows of T V contiguous doubles
-        const int row = T * V, rows_pp = tvol / T, nrow = np * rows_pp;
-        for (int i = tid; i < nrow * row; i += NT) {
-            const int rw = i / row, x = i - rw * row;
-            const int pp = rw / rows_pp, rr = rw - pp * rows_pp;
-            const long c = DIM == 3 ? ((long)(rr / T + off) * S + (rr % T + off)) * S + off : (long)(rr + off) * S + off;
-            img[i] = src[(pp * svol + c) * V + x];
-        }
-    }
-    __syncthreads();
-
-    int tst[3], dst[3];                                           // volume strides of the window and of delta's box
+// volume strides of the window and of delta's box
+template <int DIM> __device__ __forceinline__ void fv_muscl_strides(int T, int D, int (&tst)[3], int (&dst)[3]) {
     if constexpr (DIM == 3) { tst[0] = T * T; tst[1] = T; tst[2] = 1; dst[0] = D * D; dst[1] = D; dst[2] = 1; }
     else { tst[0] = T; tst[1] = 1; tst[2] = 0; dst[0] = D; dst[1] = 1; dst[2] = 0; }
-    const double hr = 0.5 * r;
+}
 
-    // ---- phase 1: delta of every plus-shape volume (box coordinates 0 .. P + 1, at most one of them outside 1 .. P)
+// phase 1 of a workgroup whose `np` windows stand in img: delta of every plus-shape volume (box coordinates 0 .. P + 1, at most one of them
+// outside 1 .. P) -> del
+template <int DIM, class PDE, int NT>
+__device__ __forceinline__ void fv_muscl_predict(const double* img, double* del, const long* __restrict__ slot, long first, int np, int P, int m, int V,
+                                                 double r) {
+    const int T = P + 4, D = P + 2;
+    const int tvol = fvm_pow<DIM>(T), dvol = fvm_pow<DIM>(D);
+    const int tid = (int)threadIdx.x;
+    int tst[3], dst[3];
+    fv_muscl_strides<DIM>(T, D, tst, dst);
+    const double hr = 0.5 * r;
     for (int i = tid; i < np * dvol; i += NT) {
         const int pp = i / dvol, dc = i - pp * dvol;
         if (slot && slot[first + pp] < 0) continue;
@@ -137,9 +115,21 @@ fv_muscl_kernel(double* __restrict__ Q, double* __restrict__ out, const long* __
         for (int v = 0; v < FVM_MAXV; v++)
             if (v < m) dl[v] = -hr * sum[v];
     }
-    __syncthreads();
+}
 
-    // ---- phase 2: the interior volumes
+// phase 2: the interior volumes of the `np` patches.  out == nullptr: in place into Q (layout with halo H); else halo-less out [patch][P^DIM][V],
+// auxiliary variables copied.  LAM: -> the largest eigenvalue over the directions of the NEW states this lane stored (nan_max: a NaN survives),
+// evaluated on the values as the arrays hold them -- what a scan of `out` would read
+template <int DIM, class PDE, int NT, bool LAM>
+__device__ __forceinline__ double fv_muscl_correct(const double* img, const double* del, double* __restrict__ Q, double* __restrict__ out,
+                                                   const long* __restrict__ slot, long first, int np, int P, int H, int m, int V, double r) {
+    const int S = P + 2 * H, T = P + 4, D = P + 2;
+    const int tvol = fvm_pow<DIM>(T), dvol = fvm_pow<DIM>(D), ncell = fvm_pow<DIM>(P);
+    const long svol = DIM == 3 ? (long)S * S * S : (long)S * S;
+    const int tid = (int)threadIdx.x;
+    int tst[3], dst[3];
+    fv_muscl_strides<DIM>(T, D, tst, dst);
+    [[maybe_unused]] double lmax = 0.0;
     for (int i = tid; i < np * ncell; i += NT) {
         const int pp = i / ncell, id = i - pp * ncell;
         const long patch = first + pp;
@@ -179,6 +169,13 @@ fv_muscl_kernel(double* __restrict__ Q, double* __restrict__ out, const long* __
             for (int v = 0; v < FVM_MAXV; v++)
                 if (v < m) o[v] = qc[v] - r * acc[v];
             for (int v = m; v < V; v++) o[v] = q[v];
+            if constexpr (LAM) {
+                double qn[FVM_MAXV];
+#pragma unroll
+                for (int v = 0; v < FVM_MAXV; v++) qn[v] = v < m ? qc[v] - r * acc[v] : (v < V ? q[v] : 0.0);
+#pragma unroll
+                for (int d = 0; d < DIM; d++) lmax = nan_max(lmax, PDE::maxeig(qn, d));
+            }
         } else {
             const long c = DIM == 3 ? ((long)(co[0] + H) * S + (co[1] + H)) * S + (co[2] + H) : (long)(co[0] + H) * S + (co[1] + H);
             double* o = Q + (patch * svol + c) * V;
@@ -187,6 +184,49 @@ fv_muscl_kernel(double* __restrict__ Q, double* __restrict__ out, const long* __
                 if (v < m) o[v] = qc[v] - r * acc[v];
         }
     }
+    return lmax;
+}
+
+template <int DIM, class PDE, int NT>
+__global__ void __launch_bounds__(NT)
+fv_muscl_kernel(double* __restrict__ Q, double* __restrict__ out, const long* __restrict__ slot, int P, int H, int m, int V, double r,
+                long n_patches, int ppb) {
+    extern __shared__ __attribute__((aligned(16))) double fvm_lds[];
+    const int S = P + 2 * H, T = P + 4, off = H - 2;
+    const int tvol = fvm_pow<DIM>(T);
+    const long svol = DIM == 3 ? (long)S * S * S : (long)S * S;
+    double* img = fvm_lds;                                        // [patch slot][T^DIM][V]
+    double* del = fvm_lds + (long)ppb * tvol * V;                 // [patch slot][(P + 2)^DIM][m]
+    const long first = (long)blockIdx.x * ppb;
+    const int np = (int)(n_patches - first < ppb ? n_patches - first : ppb);
+    const int tid = (int)threadIdx.x;
+
+    // ---- stage the windows
+    const double* src = Q + first * svol * V;
+    if (off == 0) {                                               // the window is the patch: one contiguous block
+        const int total = np * tvol * V;
+        if ((reinterpret_cast<unsigned long long>(src) & 15) == 0) {
+            const fvm_v2d* s2 = reinterpret_cast<const fvm_v2d*>(src);
+            fvm_v2d* d2 = reinterpret_cast<fvm_v2d*>(img);
+            for (int i = tid; i < total / 2; i += NT) d2[i] = s2[i];
+            if ((total & 1) && tid == 0) img[total - 1] = src[total - 1];
+        } else {
+            for (int i = tid; i < total; i += NT) img[i] = src[i];
+        }
+    } else {                                                      // H > 2: rows of T V contiguous doubles
+        const int row = T * V, rows_pp = tvol / T, nrow = np * rows_pp;
+        for (int i = tid; i < nrow * row; i += NT) {
+            const int rw = i / row, x = i - rw * row;
+            const int pp = rw / rows_pp, rr = rw - pp * rows_pp;
+            const long c = DIM == 3 ? ((long)(rr / T + off) * S + (rr % T + off)) * S + off : (long)(rr + off) * S + off;
+            img[i] = src[(pp * svol + c) * V + x];
+        }
+    }
+    __syncthreads();
+
+    fv_muscl_predict<DIM, PDE, NT>(img, del, slot, first, np, P, m, V, r);
+    __syncthreads();
+    fv_muscl_correct<DIM, PDE, NT, false>(img, del, Q, out, slot, first, np, P, H, m, V, r);
 }
 
 // launch for one (DIM, PDE); the plan (patches per workgroup, LDS bytes) is fv_muscl_plan's, which exa_fv_plan_create has checked
@@ -217,6 +257,157 @@ int fv_muscl_run(int P, int H, int m, int V, long n_patches, double* Q, double d
         if (pl.nt == 512) return go(fv_muscl_kernel<DIM, PDE, 512>, 512);
     }
     return go(fv_muscl_kernel<DIM, PDE, 256>, 256);
+}
+
+// ---- the GRID step (exa_fv_grid_step_muscl_device): the patches are the cells of a Cartesian grid g[0] x g[1] (x g[2]), patch index row-major,
+// Q and out are HALO-LESS [patch][P^DIM][V] (P >= 2), Q is only read.  Only the staging differs from fv_muscl_kernel: the window of a patch is
+// gathered from the patch, its face neighbours AND its diagonal neighbours (the edge entries), every outside axis resolved on its own --
+//   inside the domain or a periodic face   the neighbour patch along that axis (wrap), in-patch coordinate c -+ P
+//   FV_FACE_MIRROR at the patch's domain face   the patch's own coordinate -1 - c (low) / 2 P - 1 - c (high), every variable times the face's sign
+//   FV_FACE_STATE                               the face's state
+// -- and two outside axes composed in axis order, the later axis last (what a halo fill axis after axis over the full transverse range leaves,
+// solvers.fill_halos_boundary; the rule of exa_lim_project_patches_halo2): walking from the last axis down, the first state met is the value, times
+// the signs of the mirrors met before it; without a state the source volume times all mirror signs.  The entries no update reads (a second layer
+// together with another outside coordinate, the 3-D corners) are not written: phase 1 keeps to the plus shape, phase 2 to what the header lists.
+// Neighbours live in other workgroups, which is why the new states go to a second array.
+
+// grid coordinates of a patch (32-bit arithmetic; the launcher has checked n_patches < 2^32)
+template <int DIM> __device__ __forceinline__ void fv_muscl_patch_coords(const FvMusclGrid& ga, long patch, int (&pg)[3]) {
+    unsigned x = (unsigned)patch;
+    if constexpr (DIM == 3) { pg[2] = (int)(x % (unsigned)ga.g[2]); x /= (unsigned)ga.g[2]; } else pg[2] = 0;
+    pg[1] = (int)(x % (unsigned)ga.g[1]);
+    pg[0] = (int)(x / (unsigned)ga.g[1]);
+}
+
+// where the window entry at interior coordinates c (each in -2 .. P + 1) of the patch at pg finds its V doubles; mirrors: bit (axis * 2 + side) set
+// for every mirror face whose signs multiply them.  fbits: two bits per face, 0 where every face is periodic
+template <int DIM>
+__device__ __forceinline__ const double* fv_muscl_grid_source(const double* __restrict__ Q, const FvMusclGrid& ga, unsigned fbits, const int (&pg)[3],
+                                                              const int (&c)[3], int P, int V, unsigned& mirrors) {
+    int pn[3] = {pg[0], pg[1], pg[2]}, cn[3] = {c[0], c[1], c[2]};
+    mirrors = 0u;
+    const double* state = nullptr;
+    static_for_muscl<0, DIM>([&](auto kk) {
+        constexpr int a = DIM - 1 - decltype(kk)::value;          // the later axis first: it was filled last
+        if (state || (c[a] >= 0 && c[a] < P)) return;
+        const int side = c[a] < 0 ? 0 : 1, face = a * 2 + side;
+        const bool at_face = side == 0 ? pg[a] == 0 : pg[a] == ga.g[a] - 1;
+        const int kind = at_face ? (int)((fbits >> (2 * face)) & 3u) : FV_FACE_PERIODIC;
+        if (kind == FV_FACE_STATE) { state = ga.bstate + face * V; return; }
+        if (kind == FV_FACE_MIRROR) {
+            cn[a] = (side == 0 ? -1 : 2 * P - 1) - c[a];
+            mirrors |= 1u << face;
+            return;
+        }
+        pn[a] += side == 0 ? -1 : 1;
+        if (pn[a] < 0) pn[a] += ga.g[a];
+        if (pn[a] >= ga.g[a]) pn[a] -= ga.g[a];
+        cn[a] = side == 0 ? c[a] + P : c[a] - P;
+    });
+    if (state) return state;
+    const long np = DIM == 3 ? ((long)pn[0] * ga.g[1] + pn[1]) * ga.g[2] + pn[2] : (long)pn[0] * ga.g[1] + pn[1];
+    const int cl = DIM == 3 ? (cn[0] * P + cn[1]) * P + cn[2] : cn[0] * P + cn[1];
+    return Q + (np * fvm_pow<DIM>(P) + cl) * V;
+}
+
+// wave-level maximum -> one integer atomic max per wave, issued only where it exceeds what is there (non-negative doubles order like their bit
+// patterns, a NaN lies above them all; the launcher zeroed lam)
+__device__ __forceinline__ void fv_muscl_lam_commit(double* lam, double mx) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) mx = nan_max(mx, __shfl_xor(mx, o, 64));
+    if ((threadIdx.x & 63) == 0) {
+        unsigned long long* at = reinterpret_cast<unsigned long long*>(lam);
+        const unsigned long long bits = (unsigned long long)__double_as_longlong(mx);
+        if (bits > __hip_atomic_load(at, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) atomicMax(at, bits);
+    }
+}
+
+template <int DIM, class PDE, int NT>
+__global__ void __launch_bounds__(NT)
+fv_muscl_grid_kernel(const double* __restrict__ Q, double* __restrict__ out, int P, int m, int V, double r, long n_patches, int ppb, FvMusclGrid ga) {
+    extern __shared__ __attribute__((aligned(16))) double fvm_lds[];
+    const int T = P + 4;
+    const int tvol = fvm_pow<DIM>(T);
+    double* img = fvm_lds;                                        // [patch slot][T^DIM][V]
+    double* del = fvm_lds + (long)ppb * tvol * V;                 // [patch slot][(P + 2)^DIM][m]
+    const long first = (long)blockIdx.x * ppb;
+    const int np = (int)(n_patches - first < ppb ? n_patches - first : ppb);
+    const int tid = (int)threadIdx.x;
+    unsigned fbits = 0u;                                          // kinds of the domain faces (launch-uniform)
+    if (ga.bstate) {
+#pragma unroll
+        for (int f = 0; f < 2 * DIM; f++) fbits |= (unsigned)ga.bkind[f] << (2 * f);
+    }
+
+    // ---- stage the windows: one task per window volume, V doubles each
+    for (int i = tid; i < np * tvol; i += NT) {
+        const int pp = i / tvol, tv = i - pp * tvol;
+        int c[3];                                                 // interior coordinates -2 .. P + 1
+        if constexpr (DIM == 3) { c[0] = tv / (T * T) - 2; c[1] = (tv / T) % T - 2; c[2] = tv % T - 2; }
+        else { c[0] = tv / T - 2; c[1] = tv % T - 2; c[2] = 0; }
+        int outside = 0, second = 0;
+#pragma unroll
+        for (int a = 0; a < DIM; a++) { outside += (c[a] < 0 || c[a] >= P) ? 1 : 0; second += (c[a] < -1 || c[a] > P) ? 1 : 0; }
+        if (outside > 2 || (outside == 2 && second > 0)) continue;            // no update reads it
+        int pg[3];
+        fv_muscl_patch_coords<DIM>(ga, first + pp, pg);
+        unsigned mirrors;
+        const double* src = fv_muscl_grid_source<DIM>(Q, ga, fbits, pg, c, P, V, mirrors);
+        double* dst = img + (long)i * V;
+        if (mirrors == 0u) {
+            for (int v = 0; v < V; v++) dst[v] = src[v];
+        } else {
+            for (int v = 0; v < V; v++) {
+                double x = src[v];
+#pragma unroll
+                for (int f = 0; f < 2 * DIM; f++)
+                    if ((mirrors >> f) & 1u) x *= ga.bstate[f * V + v];
+                dst[v] = x;
+            }
+        }
+    }
+    __syncthreads();
+
+    fv_muscl_predict<DIM, PDE, NT>(img, del, nullptr, first, np, P, m, V, r);
+    __syncthreads();
+    const double lmax = fv_muscl_correct<DIM, PDE, NT, true>(img, del, nullptr, out, nullptr, first, np, P, 2, m, V, r);
+    if (ga.lam) fv_muscl_lam_commit(ga.lam, lmax);
+}
+
+// launch of the grid step for one (DIM, PDE): the plan is fv_muscl_plan's, unchanged
+template <int DIM, class PDE>
+int fv_muscl_grid_run(int P, int m, int V, long n_patches, const double* Q, double* out, double dt, double h, const FvMusclGrid& ga, hipStream_t s) {
+    FvMusclPlan pl;
+    if (!fv_muscl_plan(DIM, P, m, V, &pl)) {
+        set_error("MUSCL-Hancock: the patch needs %zu B of LDS, %zu B are available", pl.lds, FV_MUSCL_LDS_AVAILABLE);
+        return -1;
+    }
+    if (P < 2) { set_error("MUSCL-Hancock grid step: patch_size must be >= 2"); return -1; }
+    if (m > FVM_MAXV) { set_error("n_real = %d exceeds %d", m, FVM_MAXV); return -1; }
+    if (!Q || !out || Q == out) { set_error("MUSCL-Hancock grid step: the new states need an array of their own"); return -1; }
+    if (n_patches > 0xffffffffL) { set_error("MUSCL-Hancock grid step: %ld patches -- a grid holds at most 2^32 - 1", n_patches); return -1; }
+    if (ga.lam) {
+        hipError_t e0 = hipMemsetAsync(ga.lam, 0, sizeof(double), s);
+        if (e0 != hipSuccess) { set_error("memset: %s", hipGetErrorString(e0)); return -2; }
+    }
+    if (n_patches <= 0) return 0;
+    const long nblk = (n_patches + pl.ppb - 1) / pl.ppb;
+    if (nblk > 0x7fffffffL) { set_error("MUSCL-Hancock: %ld patches are more than one launch covers", n_patches); return -1; }
+    const double r = dt / h;
+    auto go = [&](auto kern, int nt) -> int {
+        if (pl.lds > 64 * 1024) {
+            hipError_t ea = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)pl.lds);
+            if (ea != hipSuccess) { set_error("hipFuncSetAttribute(fv muscl grid, %zu B LDS): %s", pl.lds, hipGetErrorString(ea)); return -2; }
+        }
+        hipLaunchKernelGGL(kern, dim3((unsigned)nblk), dim3(nt), pl.lds, s, Q, out, P, m, V, r, n_patches, pl.ppb, ga);
+        hipError_t e = hipGetLastError();
+        if (e != hipSuccess) { set_error("fv_muscl grid launch: %s", hipGetErrorString(e)); return -2; }
+        return 0;
+    };
+    if constexpr (DIM == 2) {
+        if (pl.nt == 512) return go(fv_muscl_grid_kernel<DIM, PDE, 512>, 512);
+    }
+    return go(fv_muscl_grid_kernel<DIM, PDE, 256>, 256);
 }
 
 }  // namespace exa

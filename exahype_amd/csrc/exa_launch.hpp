@@ -143,6 +143,19 @@ int fv_muscl_launch(int dim, int P, int H, int n_real, int n_aux, long n_patches
                     hipStream_t s, double* out);
 int user_fv_muscl_launch(int pde, int dim, int P, int H, int n_real, int n_aux, long n_patches, double* Q, double dt, double h, const long* slot,
                          hipStream_t s, double* out);
+// the GRID step of this mode (exa_fv_grid_step_muscl_device; fv_muscl_grid_kernel): Q and out halo-less [patch][P^dim][V], the patches the cells of
+// the grid g (row-major); bstate == null: every domain face periodic, else face (axis, side) is of kind bkind[axis * 2 + side] (FV_FACE_*) with its V
+// doubles of data in bstate[(axis * 2 + side) * V ..]; lam (optional): receives the largest eigenvalue of the NEW states (zeroed by the launcher)
+struct FvMusclGrid {
+    int g[3];
+    int bkind[6];
+    const double* bstate;
+    double* lam;
+};
+int fv_muscl_grid_launch(int dim, int P, int n_real, int n_aux, long n_patches, int pde, const double* Q, double* out, double dt, double h,
+                         const FvMusclGrid* grid, hipStream_t s);
+int user_fv_muscl_grid_launch(int pde, int dim, int P, int n_real, int n_aux, long n_patches, const double* Q, double* out, double dt, double h,
+                              const FvMusclGrid* grid, hipStream_t s);
 
 void set_error(const char* fmt, ...);
 

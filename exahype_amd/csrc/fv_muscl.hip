@@ -19,4 +19,20 @@ int fv_muscl_launch(int dim, int P, int H, int n_real, int n_aux, long n_patches
     return -1;
 }
 
+int fv_muscl_grid_launch(int dim, int P, int n_real, int n_aux, long n_patches, int pde, const double* Q, double* out, double dt, double h,
+                         const FvMusclGrid* grid, hipStream_t s) {
+    const int V = n_real + n_aux;
+    if (!grid) { set_error("MUSCL-Hancock grid step: no grid"); return -1; }
+    if (pde >= 100) return user_fv_muscl_grid_launch(pde, dim, P, n_real, n_aux, n_patches, Q, out, dt, h, grid, s);
+    if (dim == 2) {
+        if (pde == 1) return fv_muscl_grid_run<2, Euler>(P, n_real, V, n_patches, Q, out, dt, h, *grid, s);
+        if (pde == 2) return fv_muscl_grid_run<2, Advection<FVM_MAXV>>(P, n_real, V, n_patches, Q, out, dt, h, *grid, s);
+    } else if (dim == 3) {
+        if (pde == 1) return fv_muscl_grid_run<3, Euler>(P, n_real, V, n_patches, Q, out, dt, h, *grid, s);
+        if (pde == 2) return fv_muscl_grid_run<3, Advection<FVM_MAXV>>(P, n_real, V, n_patches, Q, out, dt, h, *grid, s);
+    }
+    set_error("MUSCL-Hancock grid step: no kernel for dim %d, pde %d", dim, pde);
+    return -1;
+}
+
 }  // namespace exa

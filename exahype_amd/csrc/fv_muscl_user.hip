@@ -19,3 +19,20 @@ extern "C" int exa_user_fv_muscl_launch(int dim, int P, int H, int n_real, int n
     set_error("user PDE: no MUSCL-Hancock kernel for dim %d", dim);
     return -1;
 }
+
+// the grid step on halo-less arrays (exa_fv_grid_step_muscl_device); grid: exa::FvMusclGrid.  A side library built before this entry existed
+// lacks it: exa_register_pde still takes such a library, the grid step refuses its term set until it is rebuilt
+extern "C" int exa_user_fv_muscl_grid_launch(int dim, int P, int n_real, int n_aux, long n_patches, const double* Q, double* out, double dt, double h,
+                                             const void* grid, void* stream) {
+    using namespace exa;
+    const int V = n_real + n_aux;
+    if (!grid) { set_error("user PDE: MUSCL-Hancock grid step without a grid"); return -1; }
+    if (n_real > FVM_MAXV || n_real < UserPDE::NV) { set_error("user PDE evolves %d variables; n_real = %d", UserPDE::NV, n_real); return -1; }
+    const FvMusclGrid& ga = *static_cast<const FvMusclGrid*>(grid);
+    if (dim == 2) return fv_muscl_grid_run<2, UserPDE>(P, n_real, V, n_patches, Q, out, dt, h, ga, (hipStream_t)stream);
+    if constexpr (UserPDE::MAXDIM >= 3) {
+        if (dim == 3) return fv_muscl_grid_run<3, UserPDE>(P, n_real, V, n_patches, Q, out, dt, h, ga, (hipStream_t)stream);
+    }
+    set_error("user PDE: no MUSCL-Hancock grid kernel for dim %d", dim);
+    return -1;
+}

@@ -153,7 +153,8 @@ class SympyPDE:
 
         muscl_hancock=True (keyword only): the term set asks for the second-order MUSCL-Hancock patch update (FVRusanovKernel / FVPatchGrid /
         HIPPrinter with mode FV_MUSCL_HANCOCK).  The generated struct then carries HAS_MUSCL_HANCOCK and the side library one more unit
-        (csrc/fv_muscl_user.hip, exa_user_fv_muscl_launch).  The scheme -- slopes, half-step predictor, Rusanov flux of the predicted face
+        (csrc/fv_muscl_user.hip: exa_user_fv_muscl_launch and, for the one-launch grid step FVPatchGrid(fused=FUSED_EDGES),
+        exa_user_fv_muscl_grid_launch; a cached library from before that entry still registers, the grid step asks for a rebuild).  The scheme -- slopes, half-step predictor, Rusanov flux of the predicted face
         states -- is written for conservative terms of the state alone: terms that depend on position / time, an ncp or a source raise
         ValueError.  Without the keyword the generated source, the cache key and the build are what they were, and a plan in that mode on such a
         term set is refused."""

@@ -868,6 +868,9 @@ def fill_halos_boundary(Q, grid, dim, patch_size, halo_size, conditions):
     return Q
 
 
+FUSED_EDGES = "edges"      # FVPatchGrid(fused=FUSED_EDGES): the one-launch step of FV_MUSCL_HANCOCK (edge entries gathered from the diagonal patches)
+
+
 class FVPatchGrid:
     """A Cartesian grid of FV patches resident in HBM, advanced by the fused Rusanov kernel -- the role of the enclave task around the
     generated `time_step` (reference `exahype/printers/CPPPrinter.py:346`; the patch loop of `Unit test/correctness_test.cpp:118-174`).
@@ -881,6 +884,15 @@ class FVPatchGrid:
     wants it (output, the plain `time_step` entry points).  fused=False keeps the two-pass form on an array with halo (halo fill by torch ops,
     then the in-place update): the comparison the tests and the benchmark use.
 
+    mode=FV_MUSCL_HANCOCK (second order, halo_size >= 2) reads the EDGE entries of the halo too, which belong to diagonal patches.  The default
+    fused=True (face neighbours only) refuses it.  fused=FUSED_EDGES is its one-launch step (`exa_fv_grid_step_muscl_device`, patch_size >= 2):
+    states halo-less in `.U`, the window of every patch -- face halos two layers deep and the edge entries, the boundary rules composed in axis
+    order -- gathered inside the patch kernel, the next step's CFL scan reduced by the kernel that writes the states; everything said above about
+    the fused form holds for it, and its results are bit-identical to fused=False, the two-pass form of this mode (torch halo fills, in-place
+    update, a scan launch per step of run()).  Measured (profiles/fv_muscl_grid_one_launch.txt): one launch takes 2.69 ms per step of 2^20 2-D
+    patches of 4^2 volumes against 6.54 ms in two passes, and 5.48 against 8.11 ms for 32^3 3-D patches of 8^3 volumes (0.40 / 0.66 of it per step
+    of run(), scan included); neither shape is slower than the two-pass form.
+
     boundary: None (periodic); one state [V] for every domain face, or a dict {(axis, side): state} that names all 2 dim faces (prescribed states,
     `exa_fv_grid_step_device`); or a dict {(axis, side): Outflow() | Wall(...) | Dirichlet(state) | state} (exahype_amd/boundary.py,
     `exa_fv_grid_step_device_bc`), in which a face that is not named stays periodic -- the vocabulary of AderDgSolver(boundary=), so that the grid
@@ -892,15 +904,29 @@ class FVPatchGrid:
         """origin, time: physical coordinates of the grid's low corner and the start time -- reach term sets whose terms depend on position /
         time (the patch centres follow from them); step() / run() advance the time.
 
-        mode=FV_MUSCL_HANCOCK (second order) runs with halo_size >= 2 and fused=False only: its stencil reads the edge entries of the halo,
-        which belong to diagonal patches -- the halo fills of the two-pass form supply them, the one-launch step takes face neighbours only."""
+        fused: True (the default) -- the one-launch step of the first-order modes; False -- the two-pass form on an array with halo; FUSED_EDGES
+        -- the one-launch step of mode=FV_MUSCL_HANCOCK (that mode only, patch_size >= 2).
+
+        mode=FV_MUSCL_HANCOCK (second order) runs with halo_size >= 2 and fused=FUSED_EDGES or fused=False: its stencil reads the edge entries of
+        the halo, which belong to diagonal patches -- the FUSED_EDGES step gathers them in the patch kernel, the halo fills of the two-pass form
+        supply them, the one-launch step behind fused=True takes face neighbours only and refuses.  halo_size only shapes `with_halo()` under
+        FUSED_EDGES: the arrays of the step have no halo."""
+        edges = isinstance(fused, str) and fused == FUSED_EDGES
+        if isinstance(fused, str) and not edges:
+            raise ValueError("FVPatchGrid(fused=%r): True, False or FUSED_EDGES (%r)" % (fused, FUSED_EDGES))
+        if edges and mode != FV_MUSCL_HANCOCK:
+            raise ValueError("FVPatchGrid(fused=FUSED_EDGES) is the one-launch step of mode=FV_MUSCL_HANCOCK; the other modes take fused=True")
+        if edges and patch_size < 2:
+            raise ValueError("FVPatchGrid(fused=FUSED_EDGES): patch_size must be >= 2 (got %d) -- the second halo layer would belong to the "
+                             "neighbour's neighbour; fused=False serves such a grid" % patch_size)
         if mode == FV_MUSCL_HANCOCK:
             if halo_size < 2:
                 raise ValueError("FVPatchGrid(mode=FV_MUSCL_HANCOCK): the scheme reads two halo layers, halo_size must be >= 2 (got %d)" % halo_size)
-            if fused:
-                raise ValueError("FVPatchGrid(mode=FV_MUSCL_HANCOCK) needs fused=False: the one-launch grid step takes its halo states from the face "
-                                 "neighbours only, this scheme also reads the edge entries (diagonal patches); the two-pass form on the array with "
-                                 "halo fills them")
+            if fused and not edges:
+                raise ValueError("FVPatchGrid(mode=FV_MUSCL_HANCOCK) needs fused=FUSED_EDGES or fused=False: the one-launch grid step behind "
+                                 "fused=True takes its halo states from the face neighbours only, this scheme also reads the edge entries "
+                                 "(diagonal patches); fused=FUSED_EDGES gathers them in its own one-launch step, the two-pass form (fused=False) "
+                                 "on the array with halo fills them")
         torch = _torch()
         self.dim, self.grid, self.P, self.H = dim, tuple(int(g) for g in grid), patch_size, halo_size
         self.n_real, self.n_aux, self.pde = n_real, n_aux, pde
@@ -909,7 +935,8 @@ class FVPatchGrid:
         self.kernel = FVRusanovKernel(dim, patch_size, halo_size, n_real, n_aux, n_patches, pde, mode, device)
         self.lib = self.kernel.lib
         self.dev = torch.device("cuda", device)
-        self.fused = bool(fused)
+        self.fused = bool(fused)                                      # the states live halo-less in `.U`
+        self.fused_edges = edges
         V = n_real + n_aux
         if self.fused:
             self.U = torch.zeros(self.grid + (patch_size,) * dim + (V,), dtype=torch.float64, device=self.dev)
@@ -1033,7 +1060,12 @@ class FVPatchGrid:
         if self._U2 is None:
             self._U2 = torch.empty_like(self.U)
         bstate = C.c_void_p(self._bstate.data_ptr()) if self._bstate is not None else None
-        if self._kinds is not None:
+        if self.fused_edges:
+            # (one state per face, the [V] / all-faces-dict form: every kind FV_FACE_STATE; periodic: no kinds)
+            kinds = self._kinds if self._kinds is not None else ((C.c_int * (2 * self.dim))(*[_lib.FV_FACE_STATE] * (2 * self.dim)) if self._bstate is not None else None)
+            check(self.lib.exa_fv_grid_step_muscl_device(self.kernel._plan, C.c_void_p(self.U.data_ptr()), C.c_void_p(self._U2.data_ptr()), self._grid_arr,
+                                                         kinds, bstate, dt, self.h, C.c_void_p(self._lam_next.data_ptr()), _stream_ptr()))
+        elif self._kinds is not None:
             check(self.lib.exa_fv_grid_step_device_bc(self.kernel._plan, C.c_void_p(self.U.data_ptr()), C.c_void_p(self._U2.data_ptr()), self._grid_arr,
                                                       self._kinds, bstate, C.c_void_p(self.centres.data_ptr()), self.time, dt, self.h,
                                                       C.c_void_p(self._lam_next.data_ptr()), _stream_ptr()))

@@ -69,6 +69,8 @@ extern "C" {
  *     with 5 variables, <= 20 with 10; 3-D patch_size <= 8 with up to 6.  Larger 3-D patches would need plane streaming: not built.
  *   - exa_fv_grid_step_device[_bc] return EXA_ERR_INVALID: the one-launch grid step takes face neighbours only, this scheme needs the edge
  *     neighbours (diagonal patches); fill the halos of the array with halo and call exa_fv_time_step_device.
+ *   - exa_fv_grid_step_muscl_device IS the one-launch grid step of this mode, on halo-less arrays: its kernel gathers the window of a patch from
+ *     the face AND the diagonal neighbours (below, beside the grid-step entries); patch_size >= 2.
  *   - exa_fv_max_eigenvalue serves plans of this mode as it serves the others. */
 #define EXA_FV_MUSCL_HANCOCK 2
 
@@ -176,6 +178,26 @@ int exa_fv_grid_step_device(exa_fv_plan* plan, const double* Q_dev, double* QNex
 int exa_fv_grid_step_device_bc(exa_fv_plan* plan, const double* Q_dev, double* QNext_dev, const long* grid, const int* face_kind,
                                const double* face_data_dev, const double* centre_dev, double t, double dt, double h, double* lambda_next_dev,
                                void* stream);
+/* The grid step of EXA_FV_MUSCL_HANCOCK plans, ONE launch on HALO-LESS arrays: Q_dev / QNext_dev [n_patches][P^dim][n_real+n_aux] as above, Q_dev
+ * only read, QNext_dev (a different array) receives the new evolved variables and a copy of the auxiliary ones; patch index row-major over
+ * grid[dim].  face_kind / face_data_dev mean what they mean for exa_fv_grid_step_device_bc (NULL kinds: every face periodic); there is no centre /
+ * t argument, the term sets of this mode see the state alone.  The kernel assembles the window (P + 4)^dim of every patch on chip.  A window
+ * entry with interior coordinates c_a in [-2, P + 2) resolves every outside axis on its own:
+ *   inside the domain, or a periodic face     the neighbour patch along that axis (wrap), in-patch coordinate c_a -+ P
+ *   EXA_FV_FACE_MIRROR at the patch's face    the patch's own coordinate -1 - c_a (low) / 2 P - 1 - c_a (high), every variable times its sign
+ *   EXA_FV_FACE_STATE                         the face's state
+ * Where two axes are outside (the edge entries: 4 points per patch in 2-D, 12 lines in 3-D) the rules compose in axis order, the later axis last,
+ * as for exa_lim_project_patches_halo2 below: the state of the highest state axis wins and is multiplied by the mirror signs of later axes only;
+ * without a state axis the value is the source volume -- of the diagonal patch +- e_a +- e_b inside the domain -- times all mirror signs.  That is
+ * what a halo fill axis after axis over the full transverse range leaves in an array with halo (exahype_amd.solvers.fill_halos_boundary), and the
+ * arithmetic is that of exa_fv_time_step_device on such an array: the results are bit-identical.  The entries no update reads are not formed.
+ * lambda_next_dev (device, 1 double, or NULL): the largest eigenvalue of the NEW states over the directions, equal bit for bit to
+ * exa_fv_max_eigenvalue(plan, QNext_dev, 1, ...) (a NaN survives).  halo_size of the plan is not used (the arrays have none).
+ * EXA_ERR_INVALID, with a message that names the way out: a NULL plan or pointer; a plan of another mode; patch_size < 2 (the second layer would
+ * belong to the neighbour's neighbour: the two-pass form serves it); QNext_dev == Q_dev; a product of grid that is not n_patches; a kind outside
+ * 0 .. 2; a non-periodic kind without data; h <= 0; a registered term set whose side library was built before this entry existed (rebuild it). */
+int exa_fv_grid_step_muscl_device(exa_fv_plan* plan, const double* Q_dev, double* QNext_dev, const long* grid, const int* face_kind,
+                                  const double* face_data_dev, double dt, double h, double* lambda_next_dev, void* stream);
 /* CFL scan of a patch array: max over the INTERIOR volumes of all patches and over the directions of the largest eigenvalue -> lambda_dev[0]
  * (device memory; one reduction launch, nothing returns to the host).  halo_less != 0: Q_dev is a halo-less array (every volume counts).
  * centre_dev / t / h: for term sets whose terms depend on position / time. */
