@@ -13,6 +13,7 @@ PDE_EULER_REF2D, PDE_EULER, PDE_ADVECTION = 0, 1, 2
 FV_FAITHFUL, FV_RUSANOV, FV_MUSCL_HANCOCK = 0, 1, 2         # include/exahype_hip.h EXA_FV_*
 FV_FACE_PERIODIC, FV_FACE_STATE, FV_FACE_MIRROR = 0, 1, 2      # include/exahype_hip.h EXA_FV_FACE_*
 PDE_FLAG_XT, PDE_FLAG_NCP, PDE_FLAG_ADMISSIBLE, PDE_FLAG_CONSERVATIVE, PDE_FLAG_MUSCL_HANCOCK = 1, 2, 4, 8, 16      # EXA_PDE_FLAG_*
+PDE_FLAG_MUSCL_TERMS = 32
 
 # every symbol include/exahype_hip.h declares: (restype, argtypes)
 _vp, _dp, _lp = C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_long)

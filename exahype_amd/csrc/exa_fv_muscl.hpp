@@ -1,5 +1,5 @@
 // Second-order MUSCL-Hancock patch update for gfx950 (EXA_FV_MUSCL_HANCOCK) -- the templates; fv_muscl.hip instantiates them
-// for the built-in term sets, fv_muscl_user.hip for a generated one (pde_codegen.SympyPDE(muscl_hancock=True)).
+// for the built-in term sets, fv_muscl_user.hip for a generated one (pde_codegen.SympyPDE(muscl_hancock=True[, muscl_terms=True])).
 //
 // The scheme, on a patch array Q[patch][S..][V] (S = P + 2 H, H >= 2), evolved variables v < m, r = dt / h:
 //   1. slopes       s_e(c) = minmod(Q_c - Q_{c-e}, Q_{c+e} - Q_c) for every axis e, for the interior volumes and their face neighbours (the "plus
@@ -8,6 +8,12 @@
 //   3. face states  w_c^{+-d} = (Q_c +- s_d(c)/2) + delta_c
 //   4. face flux    F* = (f_d(w_L) + f_d(w_R))/2 - max(l_d(w_L), l_d(w_R))/2 (w_R - w_L)     (flux_rt / maxeig: IEEE division and square root)
 //   5. update       Q_c <- Q_c - r sum_d (F*_{c+1/2,d} - F*_{c-1/2,d}), interior volumes, evolved variables; everything else stays as it is.
+// A term set with a source S(q) and / or a non-conservative product B_d(q) dq of the state alone (HAS_MUSCL_TERMS; pde_codegen.SympyPDE(muscl_hancock=
+// True, muscl_terms=True)) adds, under `if constexpr` -- the instantiations without them are what they were, operation for operation:
+//   2. predictor    ... - (r/2) sum_e B_e(Q_c) s_e(c) + (dt/2) S(Q_c)
+//   4. face jump    D_{c+1/2,d} = B_d((w_L + w_R)/2) (w_R - w_L) on the predicted face states (fv_muscl_jump: the form of the Rusanov kernel)
+//   5. update       ... - r sum_d [1/2 (D_{c+1/2,d} + D_{c-1/2,d}) + B_d(Q_c + delta_c) s_d(c)] + dt S(Q_c + delta_c)      (midpoint rule in time)
+// Every quantity is at hand in the phase that needs it: the LDS plan and the staging are the same.  The terms see 0 for auxiliary variables.
 // An interior update reads Q at c +- e_d, c +- 2 e_d and c +- e_d +- e_e (d != e): the two halo layers next to the interior INCLUDING the edge entries
 // (layer 1 along two axes); never (+-2, +-1), the 3-D corners or a layer beyond the second.
 //
@@ -66,6 +72,17 @@ __device__ __forceinline__ void fv_muscl_face(const double (&wL)[FVM_MAXV], cons
     for (int v = 0; v < FVM_MAXV; v++) F[v] = v < m ? 0.5 * (fL[v] + fR[v]) - hl * (wR[v] - wL[v]) : 0.0;
 }
 
+// path-conservative jump term of the face (wL, wR) along D: B_D at the mean state times the jump (half of it goes to either side)
+template <class PDE, int D>
+__device__ __forceinline__ void fv_muscl_jump(const double (&wL)[FVM_MAXV], const double (&wR)[FVM_MAXV], int m, double (&out)[FVM_MAXV]) {
+    double qa[FVM_MAXV], dq[FVM_MAXV];
+#pragma unroll
+    for (int v = 0; v < FVM_MAXV; v++) { qa[v] = 0.5 * (wL[v] + wR[v]); dq[v] = wR[v] - wL[v]; out[v] = 0.0; }
+    PDE::ncp(qa, dq, D, out);
+#pragma unroll
+    for (int v = 0; v < FVM_MAXV; v++) out[v] = v < m ? out[v] : 0.0;
+}
+
 template <int DIM> __host__ __device__ constexpr int fvm_pow(int b) { return DIM == 3 ? b * b * b : b * b; }
 
 // volume strides of the window and of delta's box
@@ -78,7 +95,7 @@ template <int DIM> __device__ __forceinline__ void fv_muscl_strides(int T, int D
 // outside 1 .. P) -> del
 template <int DIM, class PDE, int NT>
 __device__ __forceinline__ void fv_muscl_predict(const double* img, double* del, const long* __restrict__ slot, long first, int np, int P, int m, int V,
-                                                 double r) {
+                                                 double r, [[maybe_unused]] double dt) {
     const int T = P + 4, D = P + 2;
     const int tvol = fvm_pow<DIM>(T), dvol = fvm_pow<DIM>(D);
     const int tid = (int)threadIdx.x;
@@ -109,11 +126,30 @@ __device__ __forceinline__ void fv_muscl_predict(const double* img, double* del,
             PDE::flux_rt(wm, e, fm);
 #pragma unroll
             for (int v = 0; v < FVM_MAXV; v++) sum[v] = e == 0 ? fp[v] - fm[v] : sum[v] + (fp[v] - fm[v]);
+            if constexpr (pde_has_ncp<PDE>::value) {              // + B_e(Q_c) s_e(c)
+                double nc[FVM_MAXV];
+#pragma unroll
+                for (int v = 0; v < FVM_MAXV; v++) nc[v] = 0.0;
+                PDE::ncp(qc, s, e, nc);
+#pragma unroll
+                for (int v = 0; v < FVM_MAXV; v++) sum[v] += nc[v];
+            }
         });
         double* dl = del + ((long)pp * dvol + dc) * m;
+        if constexpr (pde_has_source<PDE>::value) {               // + (dt/2) S(Q_c)
+            double Sq[FVM_MAXV];
 #pragma unroll
-        for (int v = 0; v < FVM_MAXV; v++)
-            if (v < m) dl[v] = -hr * sum[v];
+            for (int v = 0; v < FVM_MAXV; v++) Sq[v] = 0.0;
+            PDE::source(qc, Sq);
+            const double hdt = 0.5 * dt;
+#pragma unroll
+            for (int v = 0; v < FVM_MAXV; v++)
+                if (v < m) dl[v] = -hr * sum[v] + hdt * Sq[v];
+        } else {
+#pragma unroll
+            for (int v = 0; v < FVM_MAXV; v++)
+                if (v < m) dl[v] = -hr * sum[v];
+        }
     }
 }
 
@@ -122,7 +158,8 @@ __device__ __forceinline__ void fv_muscl_predict(const double* img, double* del,
 // evaluated on the values as the arrays hold them -- what a scan of `out` would read
 template <int DIM, class PDE, int NT, bool LAM>
 __device__ __forceinline__ double fv_muscl_correct(const double* img, const double* del, double* __restrict__ Q, double* __restrict__ out,
-                                                   const long* __restrict__ slot, long first, int np, int P, int H, int m, int V, double r) {
+                                                   const long* __restrict__ slot, long first, int np, int P, int H, int m, int V, double r,
+                                                   [[maybe_unused]] double dt) {
     const int S = P + 2 * H, T = P + 4, D = P + 2;
     const int tvol = fvm_pow<DIM>(T), dvol = fvm_pow<DIM>(D), ncell = fvm_pow<DIM>(P);
     const long svol = DIM == 3 ? (long)S * S * S : (long)S * S;
@@ -145,6 +182,11 @@ __device__ __forceinline__ double fv_muscl_correct(const double* img, const doub
         double qc[FVM_MAXV], dC[FVM_MAXV], acc[FVM_MAXV];
 #pragma unroll
         for (int v = 0; v < FVM_MAXV; v++) { qc[v] = v < m ? q[v] : 0.0; dC[v] = v < m ? dl[v] : 0.0; acc[v] = 0.0; }
+        [[maybe_unused]] double qh[FVM_MAXV];                     // the half-step state Q_c + delta_c, where the volume's own terms are taken
+        if constexpr (pde_has_ncp<PDE>::value || pde_has_source<PDE>::value) {
+#pragma unroll
+            for (int v = 0; v < FVM_MAXV; v++) qh[v] = qc[v] + dC[v];
+        }
         static_for_muscl<0, DIM>([&](auto dd) {
             constexpr int d = decltype(dd)::value;
             const int qs = tst[d] * V, ds = dst[d] * m;
@@ -156,23 +198,45 @@ __device__ __forceinline__ double fv_muscl_correct(const double* img, const doub
 #pragma unroll
             for (int v = 0; v < FVM_MAXV; v++) wN[v] = v < m ? (q[qs + v] - 0.5 * sN[v]) + dl[ds + v] : 0.0;
             fv_muscl_face<PDE, d>(wCp, wN, m, Fp);
+            [[maybe_unused]] double Dp[FVM_MAXV], Dm[FVM_MAXV];
+            if constexpr (pde_has_ncp<PDE>::value) fv_muscl_jump<PDE, d>(wCp, wN, m, Dp);
             fv_muscl_slope(q - qs, qs, m, sN);                    // the minus-side neighbour's plus state
 #pragma unroll
             for (int v = 0; v < FVM_MAXV; v++) wN[v] = v < m ? (q[v - qs] + 0.5 * sN[v]) + dl[v - ds] : 0.0;
             fv_muscl_face<PDE, d>(wN, wCm, m, Fm);
 #pragma unroll
             for (int v = 0; v < FVM_MAXV; v++) acc[v] = d == 0 ? Fp[v] - Fm[v] : acc[v] + (Fp[v] - Fm[v]);
+            if constexpr (pde_has_ncp<PDE>::value) {              // + (D_{c+1/2} + D_{c-1/2}) / 2 + B_d(Q_c + delta_c) s_d(c)
+                double Bs[FVM_MAXV];
+                fv_muscl_jump<PDE, d>(wN, wCm, m, Dm);
+#pragma unroll
+                for (int v = 0; v < FVM_MAXV; v++) Bs[v] = 0.0;
+                PDE::ncp(qh, sC, d, Bs);
+#pragma unroll
+                for (int v = 0; v < FVM_MAXV; v++)
+                    if (v < m) acc[v] += (0.5 * Dp[v] + 0.5 * Dm[v]) + Bs[v];
+            }
         });
+        [[maybe_unused]] double Sq[FVM_MAXV];                     // S(Q_c + delta_c): the source at the half-step state
+        if constexpr (pde_has_source<PDE>::value) {
+#pragma unroll
+            for (int v = 0; v < FVM_MAXV; v++) Sq[v] = 0.0;
+            PDE::source(qh, Sq);
+        }
+        auto updated = [&](int v) -> double {                     // the new value of evolved variable v
+            if constexpr (pde_has_source<PDE>::value) return (qc[v] - r * acc[v]) + dt * Sq[v];
+            else return qc[v] - r * acc[v];
+        };
         if (out) {                                                // halo-less QOut [patch][P^DIM][V]: auxiliary variables copied
             double* o = out + (patch * ncell + id) * V;
 #pragma unroll
             for (int v = 0; v < FVM_MAXV; v++)
-                if (v < m) o[v] = qc[v] - r * acc[v];
+                if (v < m) o[v] = updated(v);
             for (int v = m; v < V; v++) o[v] = q[v];
             if constexpr (LAM) {
                 double qn[FVM_MAXV];
 #pragma unroll
-                for (int v = 0; v < FVM_MAXV; v++) qn[v] = v < m ? qc[v] - r * acc[v] : (v < V ? q[v] : 0.0);
+                for (int v = 0; v < FVM_MAXV; v++) qn[v] = v < m ? updated(v) : (v < V ? q[v] : 0.0);
 #pragma unroll
                 for (int d = 0; d < DIM; d++) lmax = nan_max(lmax, PDE::maxeig(qn, d));
             }
@@ -181,7 +245,7 @@ __device__ __forceinline__ double fv_muscl_correct(const double* img, const doub
             double* o = Q + (patch * svol + c) * V;
 #pragma unroll
             for (int v = 0; v < FVM_MAXV; v++)
-                if (v < m) o[v] = qc[v] - r * acc[v];
+                if (v < m) o[v] = updated(v);
         }
     }
     return lmax;
@@ -190,7 +254,7 @@ __device__ __forceinline__ double fv_muscl_correct(const double* img, const doub
 template <int DIM, class PDE, int NT>
 __global__ void __launch_bounds__(NT)
 fv_muscl_kernel(double* __restrict__ Q, double* __restrict__ out, const long* __restrict__ slot, int P, int H, int m, int V, double r,
-                long n_patches, int ppb) {
+                long n_patches, int ppb, double dt) {
     extern __shared__ __attribute__((aligned(16))) double fvm_lds[];
     const int S = P + 2 * H, T = P + 4, off = H - 2;
     const int tvol = fvm_pow<DIM>(T);
@@ -224,9 +288,9 @@ fv_muscl_kernel(double* __restrict__ Q, double* __restrict__ out, const long* __
     }
     __syncthreads();
 
-    fv_muscl_predict<DIM, PDE, NT>(img, del, slot, first, np, P, m, V, r);
+    fv_muscl_predict<DIM, PDE, NT>(img, del, slot, first, np, P, m, V, r, dt);
     __syncthreads();
-    fv_muscl_correct<DIM, PDE, NT, false>(img, del, Q, out, slot, first, np, P, H, m, V, r);
+    fv_muscl_correct<DIM, PDE, NT, false>(img, del, Q, out, slot, first, np, P, H, m, V, r, dt);
 }
 
 // launch for one (DIM, PDE); the plan (patches per workgroup, LDS bytes) is fv_muscl_plan's, which exa_fv_plan_create has checked
@@ -248,7 +312,7 @@ int fv_muscl_run(int P, int H, int m, int V, long n_patches, double* Q, double d
             hipError_t ea = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)pl.lds);
             if (ea != hipSuccess) { set_error("hipFuncSetAttribute(fv muscl, %zu B LDS): %s", pl.lds, hipGetErrorString(ea)); return -2; }
         }
-        hipLaunchKernelGGL(kern, dim3((unsigned)nblk), dim3(nt), pl.lds, s, Q, out, slot, P, H, m, V, r, n_patches, pl.ppb);
+        hipLaunchKernelGGL(kern, dim3((unsigned)nblk), dim3(nt), pl.lds, s, Q, out, slot, P, H, m, V, r, n_patches, pl.ppb, dt);
         hipError_t e = hipGetLastError();
         if (e != hipSuccess) { set_error("fv_muscl launch: %s", hipGetErrorString(e)); return -2; }
         return 0;
@@ -324,7 +388,8 @@ __device__ __forceinline__ void fv_muscl_lam_commit(double* lam, double mx) {
 
 template <int DIM, class PDE, int NT>
 __global__ void __launch_bounds__(NT)
-fv_muscl_grid_kernel(const double* __restrict__ Q, double* __restrict__ out, int P, int m, int V, double r, long n_patches, int ppb, FvMusclGrid ga) {
+fv_muscl_grid_kernel(const double* __restrict__ Q, double* __restrict__ out, int P, int m, int V, double r, long n_patches, int ppb, FvMusclGrid ga,
+                     double dt) {
     extern __shared__ __attribute__((aligned(16))) double fvm_lds[];
     const int T = P + 4;
     const int tvol = fvm_pow<DIM>(T);
@@ -368,9 +433,9 @@ fv_muscl_grid_kernel(const double* __restrict__ Q, double* __restrict__ out, int
     }
     __syncthreads();
 
-    fv_muscl_predict<DIM, PDE, NT>(img, del, nullptr, first, np, P, m, V, r);
+    fv_muscl_predict<DIM, PDE, NT>(img, del, nullptr, first, np, P, m, V, r, dt);
     __syncthreads();
-    const double lmax = fv_muscl_correct<DIM, PDE, NT, true>(img, del, nullptr, out, nullptr, first, np, P, 2, m, V, r);
+    const double lmax = fv_muscl_correct<DIM, PDE, NT, true>(img, del, nullptr, out, nullptr, first, np, P, 2, m, V, r, dt);
     if (ga.lam) fv_muscl_lam_commit(ga.lam, lmax);
 }
 
@@ -399,7 +464,7 @@ int fv_muscl_grid_run(int P, int m, int V, long n_patches, const double* Q, doub
             hipError_t ea = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)pl.lds);
             if (ea != hipSuccess) { set_error("hipFuncSetAttribute(fv muscl grid, %zu B LDS): %s", pl.lds, hipGetErrorString(ea)); return -2; }
         }
-        hipLaunchKernelGGL(kern, dim3((unsigned)nblk), dim3(nt), pl.lds, s, Q, out, P, m, V, r, n_patches, pl.ppb, ga);
+        hipLaunchKernelGGL(kern, dim3((unsigned)nblk), dim3(nt), pl.lds, s, Q, out, P, m, V, r, n_patches, pl.ppb, ga, dt);
         hipError_t e = hipGetLastError();
         if (e != hipSuccess) { set_error("fv_muscl grid launch: %s", hipGetErrorString(e)); return -2; }
         return 0;

@@ -87,11 +87,17 @@ template <class P> struct pde_has_admissible<P, std::void_t<decltype(P::HAS_ADMI
 template <class P, class = void> struct pde_has_conservative_interface : std::false_type {};
 template <class P> struct pde_has_conservative_interface<P, std::void_t<decltype(P::HAS_CONSERVATIVE_INTERFACE)>> : std::bool_constant<P::HAS_CONSERVATIVE_INTERFACE> {};
 // Optional: `static constexpr bool HAS_MUSCL_HANCOCK = true` -- the term set asks for the second-order MUSCL-Hancock patch update
-// (exa_fv_muscl.hpp, EXA_FV_MUSCL_HANCOCK): its side library then carries its own instantiation (fv_muscl_user.hip).  Only for conservative
-// term sets of the state alone (no source, no non-conservative product): slopes, predictor and face flux use flux_rt / maxeig.
+// (exa_fv_muscl.hpp, EXA_FV_MUSCL_HANCOCK): its side library then carries its own instantiation (fv_muscl_user.hip).  Only for
+// term sets of the state alone: slopes, predictor and face flux use flux_rt / maxeig.
 // pde_codegen.SympyPDE(muscl_hancock=True) generates the marker.
 template <class P, class = void> struct pde_has_muscl_hancock : std::false_type {};
 template <class P> struct pde_has_muscl_hancock<P, std::void_t<decltype(P::HAS_MUSCL_HANCOCK)>> : std::bool_constant<P::HAS_MUSCL_HANCOCK> {};
+// Optional: `static constexpr bool HAS_MUSCL_TERMS = true` -- the term set takes its source(q, S) and / or ncp(q, dq, d, out) into the
+// second-order update: the source by the midpoint rule (dt/2 S(Q_c) in the predictor, dt S at the half-step state), the product as
+// B(Q_c) s in the predictor, the jump term of the predicted face states and B at the half-step state times the volume's own slope.
+// pde_codegen.SympyPDE(muscl_hancock=True, muscl_terms=True) generates the marker; without it fv_muscl_user.hip refuses such a term set.
+template <class P, class = void> struct pde_has_muscl_terms : std::false_type {};
+template <class P> struct pde_has_muscl_terms<P, std::void_t<decltype(P::HAS_MUSCL_TERMS)>> : std::bool_constant<P::HAS_MUSCL_TERMS> {};
 
 // The same terms for the ADER-DG kernels (tolerance 1e-10): generated term sets carry `_fast` twins whose reciprocals / square roots use the
 // fast sequences below (pde_codegen.py); a term set without them is evaluated as it is.

@@ -1434,10 +1434,11 @@ static FvCellData make_cd(double* out, const double* centre, double t, double h,
 extern "C" int exa_user_nv() { return exa::UserPDE::NV; }
 // include/exahype_hip.h EXA_PDE_FLAG_*: bit 0: the terms depend on position / time (HAS_XT), bit 1: the term set carries a non-conservative product
 // (HAS_NCP), bit 2: its own admissibility criterion (HAS_ADMISSIBLE), bit 3: the limiter's conservative interface (HAS_CONSERVATIVE_INTERFACE),
-// bit 4: the MUSCL-Hancock patch update (HAS_MUSCL_HANCOCK; fv_muscl_user.hip)
+// bit 4: the MUSCL-Hancock patch update (HAS_MUSCL_HANCOCK; fv_muscl_user.hip), bit 5: ... with the set's source / ncp in it (HAS_MUSCL_TERMS)
 extern "C" int exa_user_pde_flags() {
     return (exa::pde_has_xt<exa::UserPDE>::value ? 1 : 0) | (exa::pde_has_ncp<exa::UserPDE>::value ? 2 : 0) | (exa::pde_has_admissible<exa::UserPDE>::value ? 4 : 0) |
-           (exa::pde_has_conservative_interface<exa::UserPDE>::value ? 8 : 0) | (exa::pde_has_muscl_hancock<exa::UserPDE>::value ? 16 : 0);
+           (exa::pde_has_conservative_interface<exa::UserPDE>::value ? 8 : 0) | (exa::pde_has_muscl_hancock<exa::UserPDE>::value ? 16 : 0) |
+           (exa::pde_has_muscl_terms<exa::UserPDE>::value ? 32 : 0);
 }
 extern "C" int exa_user_fv_maxeig(int dim, int P, int H, int n_real, int n_aux, long n_patches, const double* Q, double* lam, void* stream,
                                   const double* centre, double t, double h) {

@@ -118,7 +118,7 @@ def _arity(fn):
 
 class SympyPDE:
     def __init__(self, n_vars, flux, max_eigenvalue, max_dim=3, name="user", source=None, ncp=None, max_aux=None, admissible=None, dmp=None, *,
-                 conservative_interface=False, muscl_hancock=False):
+                 conservative_interface=False, muscl_hancock=False, muscl_terms=False):
         """flux(q, d) -> n_vars expressions, max_eigenvalue(q, d) -> one, in the state symbols q; d = 0-based normal.
         source(q) -> n_vars expressions (optional): the algebraic source S(q) of q_t + div F(q) = S(q) -- the hook the
         reference's harness declares beside flux and maxEigenvalue (`Unit test/correctness_test.cpp:16-23`).  It enters the
@@ -157,7 +157,14 @@ class SympyPDE:
         exa_user_fv_muscl_grid_launch; a cached library from before that entry still registers, the grid step asks for a rebuild).  The scheme -- slopes, half-step predictor, Rusanov flux of the predicted face
         states -- is written for conservative terms of the state alone: terms that depend on position / time, an ncp or a source raise
         ValueError.  Without the keyword the generated source, the cache key and the build are what they were, and a plan in that mode on such a
-        term set is refused."""
+        term set is refused.
+
+        muscl_terms=True (keyword only, with muscl_hancock=True): the second-order update takes a source and / or an ncp of the state alone
+        (exa_fv_muscl.hpp; HAS_MUSCL_TERMS).  An explicit opt-in because it changes how the source is integrated: the midpoint rule in time
+        ((dt/2) S(Q_c) in the predictor, dt S at the half-step state) where the Rusanov update adds dt S(Q_c); the ncp enters the predictor as
+        B(Q_c) s, the faces as the jump term of the predicted states and the volume as B at the half-step state times its own slope.  Terms that
+        depend on position / time are still refused (a position dependence is reachable as an evolved variable with zero flux, e.g. a
+        bathymetry); SubcellLimiter(fv_mode=FV_MUSCL_HANCOCK) does not serve such a set."""
         if not 1 <= n_vars <= 8:
             raise ValueError("n_vars must be 1..8")
         self.n_vars, self.max_dim, self.name = n_vars, max_dim, name
@@ -222,10 +229,15 @@ class SympyPDE:
         if self.muscl_hancock and self.uses_xt:
             raise ValueError("muscl_hancock=True: the terms depend on position / time; the MUSCL-Hancock update is built for term sets of the "
                              "state alone")
-        if self.muscl_hancock and self.ncp_exprs is not None:
-            raise ValueError("muscl_hancock=True: the term set carries a non-conservative product; the MUSCL-Hancock update has no place for it yet")
-        if self.muscl_hancock and self.source_exprs is not None:
-            raise ValueError("muscl_hancock=True: the term set carries a source term; the MUSCL-Hancock update has no place for it yet")
+        self.muscl_terms = bool(muscl_terms)
+        if self.muscl_terms and not self.muscl_hancock:
+            raise ValueError("muscl_terms=True asks the MUSCL-Hancock update to take the source / ncp: it needs muscl_hancock=True")
+        if self.muscl_hancock and not self.muscl_terms and self.ncp_exprs is not None:
+            raise ValueError("muscl_hancock=True: the term set carries a non-conservative product; pass muscl_terms=True to take it into the "
+                             "MUSCL-Hancock update (predictor, face jump and volume term)")
+        if self.muscl_hancock and not self.muscl_terms and self.source_exprs is not None:
+            raise ValueError("muscl_hancock=True: the term set carries a source term; pass muscl_terms=True to take it into the MUSCL-Hancock "
+                             "update (integrated by the midpoint rule in time)")
         self._lib = None
         self._id = None
 
@@ -467,6 +479,9 @@ class SympyPDE:
         if self.muscl_hancock:
             src_member += ("    // the second-order MUSCL-Hancock patch update is built for this term set (exa_fv_muscl.hpp)\n"
                            "    static constexpr bool HAS_MUSCL_HANCOCK = true;\n")
+        if self.muscl_terms:
+            src_member += ("    // ... and that update takes the source / ncp above (midpoint rule in time, jump term of the predicted face states)\n"
+                           "    static constexpr bool HAS_MUSCL_TERMS = true;\n")
         if self.uses_xt:
             fast_cases = ["        case %d: {\n%s\n        } break;" % (d, self._block(self.flux_exprs[d], ["F[%d]" % v for v in range(n)], "            ", fast=True))
                           for d in range(self.max_dim)]

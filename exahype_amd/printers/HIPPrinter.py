@@ -301,6 +301,9 @@ class HIPPrinter(CodePrinter):
                   "//              one launch; reads two halo layers and their edge entries"] if mode == 2 else [
                   "// kernel     : fv_rusanov_kernel<%d, mode %d> -- %d statements fused into one launch, one workgroup per patch"
                   % (k.dim, mode, len(k.LHS))]
+            if mode == 2 and getattr(self.user_pde, "muscl_terms", False):
+                L += ["//              the term set's source enters by the midpoint rule in time, its non-conservative product in the predictor, as the",
+                      "//              jump term of the predicted face states and at the half-step state (SympyPDE(muscl_hancock=True, muscl_terms=True))"]
             L += [
                   "// C-ABI      : exa_fv_plan_create(dev, %d, %d, %d, %d, %d, %d, %d, %d, &plan); exa_fv_time_step_device(plan, %s, %s, h, stream)"
                   % (mode, k.dim, k.patch_size, k.halo_size, k.n_real, k.n_aux, k.n_patches, self.pde, k.items[0] if k.items else "Q",

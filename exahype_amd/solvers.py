@@ -14,8 +14,8 @@ import os
 import numpy as np
 
 from . import _lib
-from ._lib import (FV_FAITHFUL, FV_MUSCL_HANCOCK, FV_RUSANOV, PDE_ADVECTION, PDE_EULER, PDE_EULER_REF2D, PDE_FLAG_MUSCL_HANCOCK, PDE_FLAG_NCP, PDE_FLAG_XT,
-                   check, darr, larr)
+from ._lib import (FV_FAITHFUL, FV_MUSCL_HANCOCK, FV_RUSANOV, PDE_ADVECTION, PDE_EULER, PDE_EULER_REF2D, PDE_FLAG_MUSCL_HANCOCK, PDE_FLAG_MUSCL_TERMS, PDE_FLAG_NCP,
+                   PDE_FLAG_XT, check, darr, larr)
 from .boundary import Dirichlet, Outflow, Wall, coefficients as _bc_coefficients, fv_faces as _fv_faces, validate_boundary
 
 
@@ -39,7 +39,8 @@ class FVRusanovKernel:
     mode: FV_FAITHFUL (the reference's statement list), FV_RUSANOV (the corrected first-order update) or FV_MUSCL_HANCOCK -- second order:
     minmod slopes, an unsplit half-step predictor, the Rusanov flux of the predicted face states (exahype_amd/csrc/exa_fv_muscl.hpp).  That
     mode needs halo_size >= 2 and reads the EDGE entries of the two halo layers next to the interior (layer 1 along two axes) beside the
-    face entries; it serves PDE_EULER, PDE_ADVECTION and term sets generated with SympyPDE(..., muscl_hancock=True), ignores `centres` / `t`,
+    face entries; it serves PDE_EULER, PDE_ADVECTION and term sets generated with SympyPDE(..., muscl_hancock=True) (conservative terms of the
+    state alone; with muscl_terms=True also a source and / or a non-conservative product of the state alone), ignores `centres` / `t`,
     and a patch whose LDS plan does not fit a compute unit is refused when the kernel object is created."""
 
     def __init__(self, dim, patch_size, halo_size, n_real, n_aux, n_patches=1, pde=PDE_EULER_REF2D,
@@ -891,7 +892,10 @@ class FVPatchGrid:
     the fused form holds for it, and its results are bit-identical to fused=False, the two-pass form of this mode (torch halo fills, in-place
     update, a scan launch per step of run()).  Measured (profiles/fv_muscl_grid_one_launch.txt): one launch takes 2.69 ms per step of 2^20 2-D
     patches of 4^2 volumes against 6.54 ms in two passes, and 5.48 against 8.11 ms for 32^3 3-D patches of 8^3 volumes (0.40 / 0.66 of it per step
-    of run(), scan included); neither shape is slower than the two-pass form.
+    of run(), scan included); neither shape is slower than the two-pass form.  Both forms of the mode take a generated term set with a source
+    and / or a non-conservative product of the state alone (SympyPDE(muscl_hancock=True, muscl_terms=True)): the source enters by the midpoint
+    rule in time, the product in the predictor, as the jump term of the predicted face states and at the half-step state
+    (examples/advection_reaction_fv_second_order.py; profiles/fv_muscl_terms.txt).
 
     boundary: None (periodic); one state [V] for every domain face, or a dict {(axis, side): state} that names all 2 dim faces (prescribed states,
     `exa_fv_grid_step_device`); or a dict {(axis, side): Outflow() | Wall(...) | Dirichlet(state) | state} (exahype_amd/boundary.py,
@@ -1143,7 +1147,8 @@ class SubcellLimiter:
         second-order update (FVRusanovKernel) on patches with halo 2 -- face halos two layers deep and the edge entries from the diagonal
         cells (exa_lim_project_patches_halo2); the domain faces' conditions enter the projection as mirror / state faces (Outflow: a mirror
         with signs 1; Wall: a mirror with its signs; a constant Dirichlet: its state).  That mode serves one block, constant Dirichlet
-        states, term sets the second-order update serves (built-in Euler / advection, SympyPDE(muscl_hancock=True)) and patches whose
+        states, conservative term sets the second-order update serves (built-in Euler / advection, SympyPDE(muscl_hancock=True); not
+        muscl_terms=True: the limiter's restatement of the update knows neither a source nor an ncp) and patches whose
         LDS plan fits a compute unit (five variables: every 2-D order, 3-D N <= 5); anything else raises ValueError here.  Not together
         with conservative=True.
 
@@ -1226,6 +1231,9 @@ class SubcellLimiter:
                              "position / time dependence, no non-conservative product) or use fv_mode=FV_RUSANOV"
                              % (who, int(s.pde), "has position / time dependent terms or a non-conservative product" if xt_ncp
                                 else "does not carry the second-order patch update"))
+        if flags & PDE_FLAG_MUSCL_TERMS:
+            raise ValueError("%s: term set %d takes a source / non-conservative product into its second-order update (muscl_terms=True); the "
+                             "limiter's patch update knows neither term -- use fv_mode=FV_RUSANOV" % (who, int(s.pde)))
 
     def _muscl_plan(self):
         """The FV plan of the second-order update for `capacity` patches with halo 2.  A shape exa_fv_plan_create refuses (the LDS plan of one

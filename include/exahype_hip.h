@@ -62,8 +62,10 @@ extern "C" {
  *     (+-2, +-1), the 3-D corner entries or a layer beyond the second.
  *   - served by exa_fv_time_step_host / _device / _device_masked / _device_oop and by _device_at / _device_masked_at (centres and t are
  *     ignored: the term sets of this mode see the state alone); h > 0 is required, as for EXA_FV_RUSANOV.
- *   - term sets: EXA_PDE_EULER, EXA_PDE_ADVECTION and registered ones with EXA_PDE_FLAG_MUSCL_HANCOCK.  EXA_PDE_EULER_REF2D (F[4] never
- *     written) is refused.
+ *   - term sets: EXA_PDE_EULER, EXA_PDE_ADVECTION and registered ones with EXA_PDE_FLAG_MUSCL_HANCOCK: conservative terms of the state alone,
+ *     or -- with EXA_PDE_FLAG_MUSCL_TERMS -- also a source S(q) and / or a non-conservative product B(q) . grad q of the state alone (Euler with
+ *     a body force, two-layer-like coupling, a bathymetry carried as an evolved variable with zero flux).  Terms that depend on position / time
+ *     are not served in this mode.  EXA_PDE_EULER_REF2D (F[4] never written) is refused.
  *   - exa_fv_plan_create refuses (EXA_ERR_INVALID) a shape whose LDS plan -- 8 ((patch_size + 4)^dim (n_real + n_aux) + (patch_size + 2)^dim
  *     n_real) bytes for one patch -- exceeds the 160 KiB of a compute unit; the message names both figures.  Served: 2-D patch_size <= 32
  *     with 5 variables, <= 20 with 10; 3-D patch_size <= 8 with up to 6.  Larger 3-D patches would need plane streaming: not built.
@@ -95,12 +97,18 @@ int exa_register_pde(const char* library_path, int* pde_id);
  * EXA_PDE_FLAG_CONSERVATIVE -- its side library carries the limiter's conservative DG / FV interface (exa_lim_face_flux /
  * exa_lim_interface_correct below): pde_codegen.SympyPDE(conservative_interface=True), never together with XT or NCP;
  * EXA_PDE_FLAG_MUSCL_HANCOCK -- its side library carries the second-order patch update (EXA_FV_MUSCL_HANCOCK):
- * pde_codegen.SympyPDE(muscl_hancock=True), conservative terms of the state alone (no XT, no NCP, no source). */
+ * pde_codegen.SympyPDE(muscl_hancock=True), terms of the state alone (never XT).  Without the next flag such a set is conservative: no NCP, no
+ * source;
+ * EXA_PDE_FLAG_MUSCL_TERMS -- ... and that update takes the set's source and / or non-conservative product (pde_codegen.SympyPDE(
+ * muscl_hancock=True, muscl_terms=True)): the source by the midpoint rule in time, the product in the predictor, as the jump term of the
+ * predicted face states and at the half-step state times the volume's slope (exahype_amd/csrc/exa_fv_muscl.hpp).  Every entry that serves an
+ * EXA_FV_MUSCL_HANCOCK plan serves such a set; the a-posteriori limiter's second-order mode does not (its patch update knows neither term). */
 #define EXA_PDE_FLAG_XT 1
 #define EXA_PDE_FLAG_NCP 2
 #define EXA_PDE_FLAG_ADMISSIBLE 4
 #define EXA_PDE_FLAG_CONSERVATIVE 8
 #define EXA_PDE_FLAG_MUSCL_HANCOCK 16
+#define EXA_PDE_FLAG_MUSCL_TERMS 32
 int exa_pde_flags(int pde);
 
 /* ---- point-wise PDE terms (Functions.h:2-3) ---------------------------------- */
