@@ -1084,7 +1084,8 @@ struct StageBArgs {
     long lo[3], nb[3];     // box origin and extent
     const double* ghost[6];
     int tiled;             // box slots enumerated tile by tile (every nb[d] a multiple of the tile edge), else lexicographically
-    double* lam;           // CFL instantiations only: lam[0] = max(lam[0], largest eigenvalue of the corrected u over nodes and directions); zeroed by the caller
+    int idx32;             // the box's slot count fits 32 bits (shown by the host): slots are decoded with 32-bit divisions
+    double* lam;          // CFL instantiations only: lam[0] = max(lam[0], largest eigenvalue of the corrected u over nodes and directions); zeroed by the caller
 };
 
 // r5: the CFL scan of the NEXT step inside the kernel that writes u (template flag CFL; the instantiation without it is the one every fixed-dt step
@@ -1121,6 +1122,197 @@ __device__ inline void stage_b_cfl_scan(const double* unode, long b0, long nbox,
 
 __host__ __device__ constexpr int pow2ceil(int x) { int p = 1; while (p < x) p <<= 1; return p; }
 
+// ---- what a stage-B workgroup derives once (both kernels) ----
+// The box slots of a workgroup follow from blockIdx and everything else from kernel arguments, so what is below is wave-uniform: it is computed by the
+// scalar unit, once, and lives in scalar registers.  (It used to be derived by every lane in the gather and again in every pass of the update loop:
+// three 64-bit divisions each time, ~125 scalar instructions apiece, in front of the address of a load -- profiles/stage_b_chain.txt.)
+
+// coordinates in the box of slot b, as unsigned (StageBArgs::idx32: a division of ~20 scalar instructions) or as long
+template <int DIM, class I> __device__ __forceinline__ void stage_b_slot_coords(const StageBArgs& A, I b, long* cb) {
+    I cz = 0, cy, cx;
+    if (DIM == 3 && A.tiled) {
+        constexpr int TSH = EXA_STAGE_B_TILE_SHIFT, TM = (1 << TSH) - 1;
+        const I t = b >> (3 * TSH);
+        const int w = (int)(b & (I)((1 << (3 * TSH)) - 1));
+        const I tz = (I)(A.nb[2] >> TSH), ty = (I)(A.nb[1] >> TSH);
+        const I tyx = t / tz, tx = tyx / ty;
+        cz = ((t - tyx * tz) << TSH) + (I)(w & TM);
+        cy = ((tyx - tx * ty) << TSH) + (I)((w >> TSH) & TM);
+        cx = (tx << TSH) + (I)(w >> (2 * TSH));
+    } else {
+        I r = b;
+        if constexpr (DIM == 3) {
+            const I q = r / (I)A.nb[2];
+            cz = r - q * (I)A.nb[2];
+            r = q;
+        }
+        cx = r / (I)A.nb[1];
+        cy = r - cx * (I)A.nb[1];
+    }
+    cb[0] = (long)cx;
+    cb[1] = (long)cy;
+    cb[2] = (long)cz;
+}
+
+// one cell of the workgroup: coordinates in the block, index, and the two trace blocks each of its 2 DIM faces (d, side) reads
+template <int DIM> struct StageBCell {
+    long cc[3];
+    long cell;
+    const double* pm[2 * DIM];     // minus side of the face: the left neighbour's R trace (side 0) or the cell's own R trace (side 1)
+    const double* pp[2 * DIM];     // plus side: the cell's own L trace (side 0) or the right neighbour's L trace (side 1)
+};
+
+// box slot b (clamped to the box: the last workgroup of a launch with CPB > 1) -> cell; a neighbour across a block face is the ghost layer of that
+// face where there is one, else the periodic wrap
+template <int DIM, int TS>
+__device__ __forceinline__ void stage_b_decode(const StageBArgs& A, const double* __restrict__ trace, long ncells, long b, long nbox, StageBCell<DIM>& C) {
+    if (b >= nbox) b = nbox - 1;
+    long cb[3];
+    if (A.idx32) stage_b_slot_coords<DIM, unsigned>(A, (unsigned)b, cb);
+    else stage_b_slot_coords<DIM, long>(A, b, cb);
+    C.cc[0] = A.lo[0] + cb[0];
+    C.cc[1] = A.lo[1] + cb[1];
+    C.cc[2] = (DIM == 3) ? A.lo[2] + cb[2] : 0;
+    const long* cc = C.cc;
+    const long cell = (cc[0] * A.nc[1] + cc[1]) * A.nc[2] + cc[2];
+    C.cell = cell;
+    const long cst[3] = {A.nc[1] * A.nc[2], A.nc[2], 1};
+#pragma unroll
+    for (int d = 0; d < DIM; d++) {
+        // transverse cell index on the block face (lexicographic over the other axes)
+        long tcell;
+        if constexpr (DIM == 3) tcell = d == 0 ? cc[1] * A.nc[2] + cc[2] : (d == 1 ? cc[0] * A.nc[2] + cc[2] : cc[0] * A.nc[1] + cc[1]);
+        else tcell = d == 0 ? cc[1] : cc[0];
+        const double* own_l = trace + (((long)d * 2 + 0) * ncells + cell) * TS;
+        const double* own_r = trace + (((long)d * 2 + 1) * ncells + cell) * TS;
+        C.pp[d * 2] = own_l;
+        if (cc[d] > 0) C.pm[d * 2] = own_r - cst[d] * TS;
+        else if (A.ghost[d * 2 + 0]) C.pm[d * 2] = A.ghost[d * 2 + 0] + tcell * TS;
+        else C.pm[d * 2] = own_r + (A.nc[d] - 1) * cst[d] * TS;
+        C.pm[d * 2 + 1] = own_r;
+        if (cc[d] < A.nc[d] - 1) C.pp[d * 2 + 1] = own_l + cst[d] * TS;
+        else if (A.ghost[d * 2 + 1]) C.pp[d * 2 + 1] = A.ghost[d * 2 + 1] + tcell * TS;
+        else C.pp[d * 2 + 1] = own_l - (A.nc[d] - 1) * cst[d] * TS;
+    }
+}
+
+// The CPB cells of a workgroup, each decoded once.  One cell per workgroup (the large orders): the cell is a set of scalar registers and a lane picks the
+// blocks of its face from it by a select chain.  Several cells (60 faces at p = 1 in 3-D): lane c decodes cell c into a table in LDS, one barrier.
+template <int DIM, int CPB> struct StageBCells {
+    static constexpr int NFACE = 2 * DIM;
+    const StageBCell<DIM>* C;
+    template <int TS>
+    __device__ __forceinline__ void decode(StageBCell<DIM>* table, const StageBArgs& A, const double* __restrict__ trace, long ncells, long b0, long nbox) {
+        if (threadIdx.x < CPB) stage_b_decode<DIM, TS>(A, trace, ncells, b0 + threadIdx.x, nbox, table[threadIdx.x]);
+        __syncthreads();
+        C = table;
+    }
+    // a lane's face (cell-major over the workgroup's cells) -> its two trace blocks
+    __device__ __forceinline__ void pick(int face, const double*& pm, const double*& pp) const {
+        const int c = face / NFACE, f = face - c * NFACE;
+        pm = C[c].pm[f];
+        pp = C[c].pp[f];
+    }
+    __device__ __forceinline__ long cell(int c) const { return C[c].cell; }
+    __device__ __forceinline__ void coords(int c, long* cc) const {
+#pragma unroll
+        for (int a = 0; a < 3; a++) cc[a] = C[c].cc[a];
+    }
+};
+template <int DIM> struct StageBCells<DIM, 1> {
+    static constexpr int NFACE = 2 * DIM;
+    StageBCell<DIM> C;
+    template <int TS>
+    __device__ __forceinline__ void decode(StageBCell<DIM>*, const StageBArgs& A, const double* __restrict__ trace, long ncells, long b0, long nbox) {
+        stage_b_decode<DIM, TS>(A, trace, ncells, b0, nbox, C);
+    }
+    __device__ __forceinline__ void pick(int face, const double*& pm, const double*& pp) const {
+        pm = C.pm[0];
+        pp = C.pp[0];
+#pragma unroll
+        for (int k = 1; k < NFACE; k++) {
+            pm = face == k ? C.pm[k] : pm;
+            pp = face == k ? C.pp[k] : pp;
+        }
+    }
+    __device__ __forceinline__ long cell(int) const { return C.cell; }
+    __device__ __forceinline__ void coords(int, long* cc) const {
+#pragma unroll
+        for (int a = 0; a < 3; a++) cc[a] = C.cc[a];
+    }
+};
+
+// Lift coefficients cL[d][i] = dt / dx_d / w_i phi_L(i) (cR: phi_R) into LDS, one lane per entry.  The operator block is a kernel argument (scalar
+// registers): the lane picks its entries by a select chain -- no branch per node index, each with scalar loads and a wait of its own.
+template <int DIM, int N>
+__device__ __forceinline__ void stage_b_lift(double (*cL)[N], double (*cR)[N], double dt, double idx0, double idx1, double idx2, const DgOps<N>& ops) {
+    const int tid = threadIdx.x;
+    const int d = tid / N, i = tid - d * N;
+    const double h = d == 0 ? idx0 : (d == 1 || DIM == 2 ? idx1 : idx2);
+    double iw = ops.iw[0], pl = ops.phiL[0], pr = ops.phiR[0];
+#pragma unroll
+    for (int k = 1; k < N; k++) {
+        iw = i == k ? ops.iw[k] : iw;
+        pl = i == k ? ops.phiL[k] : pl;
+        pr = i == k ? ops.phiR[k] : pr;
+    }
+    if (tid < DIM * N) {
+        cL[d][i] = dt * h * iw * pl;
+        cR[d][i] = dt * h * iw * pr;
+    }
+}
+
+// The corrector update, u -= sum_d (cR_d fR_d - cL_d fL_d), element-wise over the workgroup's cells (lane = one variable of one node, coalesced), in two
+// halves.  request: all of a lane's u* loads in one group -- called once the lane's trace registers are dead (its fluxes are in fs[]) and in front of the
+// barrier that publishes fs[], so the workgroup pays ONE round trip to HBM for u*.  (In a loop, each pass loaded, waited and stored: KU round trips
+// in series.  Requested beside the trace loads instead, the KU doubles cost the eighth resident wave per SIMD: DESIGN 4.2.  Issued right behind that
+// barrier instead of in front of it, the group measured the same within 0.1 ms at 128^3 cells, p = 5: profiles/stage_b_chain.txt.)
+template <int DIM, int N, int NV, int CPB, int NT> struct StageBUpdate {
+    using G = Geo<DIM, N>;
+    static constexpr int NN = G::NN, NF = G::NF, NFACE = 2 * DIM, E = G::NN * NV;
+    static constexpr int KU = (CPB * E + NT - 1) / NT;
+
+    static __device__ __forceinline__ bool live(int task, long b0, long nbox, int& c) {
+        c = CPB == 1 ? 0 : task / E;
+        return task < CPB * E && b0 + c < nbox;
+    }
+    static __device__ __forceinline__ long offset(const StageBCells<DIM, CPB>& C, int task, int c) { return C.cell(c) * E + (task - c * E); }
+    static __device__ __forceinline__ void request(const double* u, const StageBCells<DIM, CPB>& C, long b0, long nbox, double (&us)[KU]) {
+        const int tid = threadIdx.x;
+#pragma unroll
+        for (int k = 0; k < KU; k++) {
+            int c;
+            const int task = tid + k * NT;
+            us[k] = live(task, b0, nbox, c) ? u[offset(C, task, c)] : 0.0;
+        }
+    }
+    template <bool CFL>
+    static __device__ __forceinline__ void apply(double* u, const StageBCells<DIM, CPB>& C, long b0, long nbox, const double (&us)[KU], const double* fs,
+                                        const double (*cL)[N], const double (*cR)[N], double* unode) {
+        const int tid = threadIdx.x;
+        // every request at once, here: they were issued together and under predicates, and past the joins of those branches the compiler's own
+        // bookkeeping waits in front of each pass for everything outstanding -- the previous pass's store included, KU store round trips in series
+        __builtin_amdgcn_s_waitcnt(0x0F70);             // vmcnt(0), the other counters untouched
+#pragma unroll
+        for (int k = 0; k < KU; k++) {
+            int c;
+            const int task = tid + k * NT;
+            if (!live(task, b0, nbox, c)) continue;
+            const int e = task - c * E, n = e / NV, v = e - n * NV;
+            double un = us[k];
+#pragma unroll
+            for (int d = 0; d < DIM; d++) {
+                const int i = G::coord(n, d), y = G::face_index(n, d);
+                const double fR = fs[((c * NFACE + d * 2 + 1) * NF + y) * NV + v];
+                const double fL = fs[((c * NFACE + d * 2 + 0) * NF + y) * NV + v];
+                un -= cR[d][i] * fR - cL[d][i] * fL;
+            }
+            u[offset(C, task, c)] = un;
+            if constexpr (CFL) unode[task] = un;
+        }
+    }
+};
+
 // Faces are laid out on aligned lane segments of GS = pow2ceil(Nf) lanes, 64/GS faces per wave pass:
 // the face-wide maximum eigenvalue (A.4) is a segmented butterfly of wavefront shuffles, no LDS, no
 // barrier; only the Rusanov fluxes go through LDS to reach the node-major corrector update.
@@ -1131,6 +1323,7 @@ dg_stage_b_kernel(double* __restrict__ u, const double* __restrict__ trace, Stag
     using G = Geo<DIM, N>;
     constexpr int NV = PDE::NV;
     constexpr int NN = G::NN, NF = G::NF;
+    using U = StageBUpdate<DIM, N, NV, CPB, NT>;
     __shared__ double unode[CFL ? CPB * NN * NV : 1];
     constexpr int NFACE = 2 * DIM;
     constexpr int TS = 2 * NV * NF;                     // doubles per (cell, d, side) trace
@@ -1144,45 +1337,9 @@ dg_stage_b_kernel(double* __restrict__ u, const double* __restrict__ trace, Stag
 
     const int tid = threadIdx.x;
     const long b0 = xcd_contiguous(blockIdx.x, gridDim.x) * CPB;
-    const double idx[3] = {idx0, idx1, idx2};
-    // (compile-time index into the kernarg-resident operator block: stays in SGPRs)
-#pragma unroll
-    for (int i = 0; i < N; i++) {
-        if (tid == i) {
-#pragma unroll
-            for (int d = 0; d < DIM; d++) {
-                cL[d][i] = dt * idx[d] * ops.iw[i] * ops.phiL[i];
-                cR[d][i] = dt * idx[d] * ops.iw[i] * ops.phiR[i];
-            }
-        }
-    }
-
-    // cell of box slot c
-    auto cell_of = [&](int c, long* cc) -> long {
-        long b = b0 + c;
-        if (b >= nbox) b = nbox - 1;
-        long cz = 0, cy, cx;
-        if (DIM == 3 && A.tiled) {
-            constexpr int TSH = EXA_STAGE_B_TILE_SHIFT, TM = (1 << TSH) - 1;
-            const long t = b >> (3 * TSH);
-            const int w = (int)(b & ((1 << (3 * TSH)) - 1));
-            const long tz = A.nb[2] >> TSH, ty = A.nb[1] >> TSH;
-            cz = ((t % tz) << TSH) + (w & TM);
-            cy = (((t / tz) % ty) << TSH) + ((w >> TSH) & TM);
-            cx = ((t / (tz * ty)) << TSH) + (w >> (2 * TSH));
-        } else {
-            if constexpr (DIM == 3) {
-                cz = b % A.nb[2];
-                b /= A.nb[2];
-            }
-            cy = b % A.nb[1];
-            cx = b / A.nb[1];
-        }
-        cc[0] = A.lo[0] + cx;
-        cc[1] = A.lo[1] + cy;
-        cc[2] = (DIM == 3) ? A.lo[2] + cz : 0;
-        return (cc[0] * A.nc[1] + cc[1]) * A.nc[2] + cc[2];
-    };
+    __shared__ StageBCell<DIM> cell_table[CPB];         // (CPB > 1 only)
+    StageBCells<DIM, CPB> C;
+    C.template decode<TS>(cell_table, A, trace, ncells, b0, nbox);
 
     const int seg = tid / GS, y = tid - seg * GS;
 #pragma unroll
@@ -1191,33 +1348,10 @@ dg_stage_b_kernel(double* __restrict__ u, const double* __restrict__ trace, Stag
         const bool ok = face < NFC && y < NF;
         double qm[NV], qp[NV], Fm[NV], Fp[NV];
         double lam = 0.0;
-        int d = 0;
         if (ok) {
-            const int c = face / NFACE, f = face - c * NFACE;
-            d = f >> 1;
-            const int side = f & 1;
-            long cc[3];
-            const long cell = cell_of(c, cc);
-            long cst[3];
-            cst[2] = 1;
-            cst[1] = A.nc[2];
-            cst[0] = A.nc[1] * A.nc[2];
-            // transverse cell index on the block face (lexicographic over the other axes)
-            long tcell;
-            if constexpr (DIM == 3) tcell = d == 0 ? cc[1] * A.nc[2] + cc[2] : (d == 1 ? cc[0] * A.nc[2] + cc[2] : cc[0] * A.nc[1] + cc[1]);
-            else tcell = d == 0 ? cc[1] : cc[0];
+            const int d = (face % NFACE) >> 1;
             const double *pm, *pp;
-            if (side == 0) {   // minus = left neighbour's R trace, plus = own L trace
-                pp = trace + (((long)d * 2 + 0) * ncells + cell) * TS;
-                if (cc[d] > 0) pm = trace + (((long)d * 2 + 1) * ncells + cell - cst[d]) * TS;
-                else if (A.ghost[d * 2 + 0]) pm = A.ghost[d * 2 + 0] + tcell * TS;
-                else pm = trace + (((long)d * 2 + 1) * ncells + cell + (A.nc[d] - 1) * cst[d]) * TS;
-            } else {           // minus = own R trace, plus = right neighbour's L trace
-                pm = trace + (((long)d * 2 + 1) * ncells + cell) * TS;
-                if (cc[d] < A.nc[d] - 1) pp = trace + (((long)d * 2 + 0) * ncells + cell + cst[d]) * TS;
-                else if (A.ghost[d * 2 + 1]) pp = A.ghost[d * 2 + 1] + tcell * TS;
-                else pp = trace + (((long)d * 2 + 0) * ncells + cell - (A.nc[d] - 1) * cst[d]) * TS;
-            }
+            C.pick(face, pm, pp);
 #pragma unroll
             for (int v = 0; v < NV; v++) {
                 qm[v] = pm[v * NF + y];
@@ -1236,24 +1370,12 @@ dg_stage_b_kernel(double* __restrict__ u, const double* __restrict__ trace, Stag
                 fs[(face * NF + y) * NV + v] = 0.5 * (Fm[v] + Fp[v]) - 0.5 * lam * (qp[v] - qm[v]);
         }
     }
+    stage_b_lift<DIM, N>(cL, cR, dt, idx0, idx1, idx2, ops);
+    double us[U::KU];
+    __builtin_amdgcn_sched_barrier(0);                  // (the requests stay behind the flux stores: the trace registers are free by now)
+    U::request(u, C, b0, nbox, us);
     __syncthreads();
-    for (int task = tid; task < CPB * NN * NV; task += NT) {
-        const int c = task / (NN * NV), e = task - c * (NN * NV);
-        if (b0 + c >= nbox) continue;
-        const int n = e / NV, v = e - n * NV;
-        long cc[3];
-        const long cell = cell_of(c, cc);
-        double un = u[cell * (NN * NV) + e];
-#pragma unroll
-        for (int d = 0; d < DIM; d++) {
-            const int i = G::coord(n, d), yy = G::face_index(n, d);
-            const double fR = fs[((c * NFACE + d * 2 + 1) * NF + yy) * NV + v];
-            const double fL = fs[((c * NFACE + d * 2 + 0) * NF + yy) * NV + v];
-            un -= cR[d][i] * fR - cL[d][i] * fL;
-        }
-        u[cell * (NN * NV) + e] = un;
-        if constexpr (CFL) unode[task] = un;
-    }
+    U::template apply<CFL>(u, C, b0, nbox, us, fs, cL, cR, unode);
     if constexpr (CFL) {
         __syncthreads();
         stage_b_cfl_scan<DIM, PDE, CPB, NN, NT>(unode, b0, nbox, A.lam);
@@ -1270,6 +1392,7 @@ dg_stage_b_dense_kernel(double* __restrict__ u, const double* __restrict__ trace
     using G = Geo<DIM, N>;
     constexpr int NV = PDE::NV;
     constexpr int NN = G::NN, NF = G::NF;
+    using U = StageBUpdate<DIM, N, NV, CPB, NT>;
     __shared__ double unode[CFL ? CPB * NN * NV : 1];
     constexpr int NFACE = 2 * DIM;
     constexpr int TS = 2 * NV * NF;                     // doubles per (cell, d, side) trace
@@ -1280,77 +1403,22 @@ dg_stage_b_dense_kernel(double* __restrict__ u, const double* __restrict__ trace
 
     const int tid = threadIdx.x;
     const long b0 = xcd_contiguous(blockIdx.x, gridDim.x) * CPB;
-    const double idx[3] = {idx0, idx1, idx2};
-    // (compile-time index into the kernarg-resident operator block: stays in SGPRs)
-#pragma unroll
-    for (int i = 0; i < N; i++) {
-        if (tid == i) {
-#pragma unroll
-            for (int d = 0; d < DIM; d++) {
-                cL[d][i] = dt * idx[d] * ops.iw[i] * ops.phiL[i];
-                cR[d][i] = dt * idx[d] * ops.iw[i] * ops.phiR[i];
-            }
-        }
-    }
-
-    // cell of box slot c
-    auto cell_of = [&](int c, long* cc) -> long {
-        long b = b0 + c;
-        if (b >= nbox) b = nbox - 1;
-        long cz = 0, cy, cx;
-        if (DIM == 3 && A.tiled) {
-            constexpr int TSH = EXA_STAGE_B_TILE_SHIFT, TM = (1 << TSH) - 1;
-            const long t = b >> (3 * TSH);
-            const int w = (int)(b & ((1 << (3 * TSH)) - 1));
-            const long tz = A.nb[2] >> TSH, ty = A.nb[1] >> TSH;
-            cz = ((t % tz) << TSH) + (w & TM);
-            cy = (((t / tz) % ty) << TSH) + ((w >> TSH) & TM);
-            cx = ((t / (tz * ty)) << TSH) + (w >> (2 * TSH));
-        } else {
-            if constexpr (DIM == 3) {
-                cz = b % A.nb[2];
-                b /= A.nb[2];
-            }
-            cy = b % A.nb[1];
-            cx = b / A.nb[1];
-        }
-        cc[0] = A.lo[0] + cx;
-        cc[1] = A.lo[1] + cy;
-        cc[2] = (DIM == 3) ? A.lo[2] + cz : 0;
-        return (cc[0] * A.nc[1] + cc[1]) * A.nc[2] + cc[2];
-    };
+    __shared__ StageBCell<DIM> cell_table[CPB];         // (CPB > 1 only)
+    StageBCells<DIM, CPB> C;
+    C.template decode<TS>(cell_table, A, trace, ncells, b0, nbox);
 
     double qm[KB][NV], qp[KB][NV], Fm[KB][NV], Fp[KB][NV];
 #pragma unroll
     for (int k = 0; k < KB; k++) {
         const int task = tid + k * NT;
-        if (task < CPB * NFACE * NF) {
-            const int c = task / (NFACE * NF);
-            int r = task - c * (NFACE * NF);
-            const int f = r / NF, y = r - f * NF;
-            const int d = f >> 1, face = f & 1;
-            long cc[3];
-            const long cell = cell_of(c, cc);
-            long cst[3];
-            cst[2] = 1;
-            cst[1] = A.nc[2];
-            cst[0] = A.nc[1] * A.nc[2];
-            // transverse cell index on the block face (lexicographic over the other axes)
-            long tcell;
-            if constexpr (DIM == 3) tcell = d == 0 ? cc[1] * A.nc[2] + cc[2] : (d == 1 ? cc[0] * A.nc[2] + cc[2] : cc[0] * A.nc[1] + cc[1]);
-            else tcell = d == 0 ? cc[1] : cc[0];
+        const int cf = task / NF;                       // (c, f) flattened
+        const bool ok = task < CPB * NFACE * NF;
+        double l = 0.0;
+        if (ok) {
+            const int c = cf / NFACE, f = cf - c * NFACE, y = task - cf * NF;
+            const int d = f >> 1;
             const double *pm, *pp;
-            if (face == 0) {   // minus = left neighbour's R trace, plus = own L trace
-                pp = trace + (((long)d * 2 + 0) * ncells + cell) * TS;
-                if (cc[d] > 0) pm = trace + (((long)d * 2 + 1) * ncells + cell - cst[d]) * TS;
-                else if (A.ghost[d * 2 + 0]) pm = A.ghost[d * 2 + 0] + tcell * TS;
-                else pm = trace + (((long)d * 2 + 1) * ncells + cell + (A.nc[d] - 1) * cst[d]) * TS;
-            } else {           // minus = own R trace, plus = right neighbour's L trace
-                pm = trace + (((long)d * 2 + 1) * ncells + cell) * TS;
-                if (cc[d] < A.nc[d] - 1) pp = trace + (((long)d * 2 + 0) * ncells + cell + cst[d]) * TS;
-                else if (A.ghost[d * 2 + 1]) pp = A.ghost[d * 2 + 1] + tcell * TS;
-                else pp = trace + (((long)d * 2 + 0) * ncells + cell - (A.nc[d] - 1) * cst[d]) * TS;
-            }
+            C.pick(cf, pm, pp);
 #pragma unroll
             for (int v = 0; v < NV; v++) {
                 qm[k][v] = pm[v * NF + y];
@@ -1359,13 +1427,16 @@ dg_stage_b_dense_kernel(double* __restrict__ u, const double* __restrict__ trace
                 Fp[k][v] = pp[(NV + v) * NF + y];
             }
             if constexpr (pde_has_xt<PDE>::value) {
+                long cc[3];
                 double xf[3];
-                face_node_coords<DIM, N>(geo, cc, d, face, y, xf);
-                lam[task] = fmax(PDE::maxeig_xt(qm[k], xf, geo.t + 0.5 * dt, d), PDE::maxeig_xt(qp[k], xf, geo.t + 0.5 * dt, d));
+                C.coords(c, cc);
+                face_node_coords<DIM, N>(geo, cc, d, f & 1, y, xf);
+                l = fmax(PDE::maxeig_xt(qm[k], xf, geo.t + 0.5 * dt, d), PDE::maxeig_xt(qp[k], xf, geo.t + 0.5 * dt, d));
             } else {
-                lam[task] = fmax(PDE::maxeig(qm[k], d), PDE::maxeig(qp[k], d));
+                l = fmax(PDE::maxeig(qm[k], d), PDE::maxeig(qp[k], d));
             }
         }
+        if (ok) lam[task] = l;
     }
     __syncthreads();
 #pragma unroll
@@ -1392,7 +1463,7 @@ dg_stage_b_dense_kernel(double* __restrict__ u, const double* __restrict__ trace
                 }
                 if constexpr (pde_has_xt<PDE>::value) {
                     long cc[3];
-                    cell_of(c, cc);
+                    C.coords(c, cc);
                     face_node_coords<DIM, N>(geo, cc, d, face, y, xf);
                 }
                 fv_ncp<PDE>(qa, dq, xf, geo.t + 0.5 * dt, d, Dj);
@@ -1401,29 +1472,18 @@ dg_stage_b_dense_kernel(double* __restrict__ u, const double* __restrict__ trace
             }
         }
     }
+    stage_b_lift<DIM, N>(cL, cR, dt, idx0, idx1, idx2, ops);
+    double us[U::KU];
+    __builtin_amdgcn_sched_barrier(0);                  // (the requests stay behind the flux stores: the trace registers are free by now)
+    U::request(u, C, b0, nbox, us);
     __syncthreads();
-    for (int task = tid; task < CPB * NN * NV; task += NT) {
-        const int c = task / (NN * NV), e = task - c * (NN * NV);
-        if (b0 + c >= nbox) continue;
-        const int n = e / NV, v = e - n * NV;
-        long cc[3];
-        const long cell = cell_of(c, cc);
-        double un = u[cell * (NN * NV) + e];
-#pragma unroll
-        for (int d = 0; d < DIM; d++) {
-            const int i = G::coord(n, d), y = G::face_index(n, d);
-            const double fR = fs[((c * NFACE + d * 2 + 1) * NF + y) * NV + v];
-            const double fL = fs[((c * NFACE + d * 2 + 0) * NF + y) * NV + v];
-            un -= cR[d][i] * fR - cL[d][i] * fL;
-        }
-        u[cell * (NN * NV) + e] = un;
-        if constexpr (CFL) unode[task] = un;
-    }
+    U::template apply<CFL>(u, C, b0, nbox, us, fs, cL, cR, unode);
     if constexpr (CFL) {
         __syncthreads();
         stage_b_cfl_scan<DIM, PDE, CPB, NN, NT>(unode, b0, nbox, A.lam);
     }
 }
+
 
 // max eigenvalue over all nodes / directions (CFL)
 template <int DIM, class PDE>
