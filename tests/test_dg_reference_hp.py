@@ -5,6 +5,8 @@
    tests/test_user_pde.py compares with) must match it to 1e-13 of the per-variable increment (tests/util.py dg_err) at the CFL-0.9 step.
 2. Every case table of the GPU parity tests (tests/dg_cases.py), with the oracle as `got`: each n_it > 0 case must see its last Picard
    iteration (the mutant with n_it - 1 iterations >= 100 * DG_TOL).  A step shrunk until the case goes blind fails here.
+3. The sharded tables (tests/test_gpu_distributed.py) on every rank's cells of the global result: the same, and a block stepped alone (no ghosts),
+   a shard evaluated without its offset and a rank that keeps its own CFL maximum are all seen.  (The limited ones: tests/test_limiter.py.)
 """
 import numpy as np
 import pytest
@@ -13,7 +15,7 @@ import oracle
 from oracle import aderdg_numpy as A
 from oracle.dg_operators import operators, operators_hp
 from tests import dg_cases as C
-from tests.util import ADV_A, cfl_dt, dg_err, euler_dg_state
+from tests.util import ADV_A, DG_TOL, cfl_dt, dg_err, dg_max_eigenvalue, euler_dg_state
 
 HP_TOL = 1e-13
 
@@ -162,3 +164,59 @@ def test_one_kernel_cases_see_the_last_iteration(nc, n_picard):
     steps = len(dts) if np.prod(nc) < 100 else 3
     for k in ((2, steps) if steps > 2 else (steps,)):
         r.check_steps(r.steps(k, dts=dts), k, dts=dts)
+
+
+# ---- the sharded cases (tests/test_gpu_distributed.py), on every rank's cells: last iteration seen, ghosts seen, shard offset seen ------------
+@pytest.mark.parametrize("N,nc,pdims,one_kernel", C.SHARDED_CASES)
+def test_sharded_cases_see_the_last_iteration_and_the_ghosts(N, nc, pdims, one_kernel):
+    G, u, dx, dts = C.sharded_input(N, nc, pdims)
+    u, want, mutant = C.steps_ref(u, dx, N, G, dts)
+    C.check_rank_slices(u, want, mutant, C.rank_slices(nc, pdims), lambda r, sl: C.steps_ref(u[sl], dx, N, nc, dts)[1], what="sharded %s" % (G,))
+
+
+@pytest.mark.parametrize("N,nc,limited", [c for c in C.SHARDED_SELF_CASES if not c[2]])
+def test_sharded_self_cases_see_the_last_iteration(N, nc, limited):
+    """(one rank that is its own neighbour: the block alone IS the grid, there is no second run to tell it from)"""
+    G, u, dx, dts = C.sharded_self_input(N, nc, limited)
+    u, want, mutant = C.steps_ref(u, dx, N, G, dts)
+    C.check_rank_slices(u, want, mutant, C.rank_slices(nc, [1, 1, 1]), what="rccl to self %s" % (G,))
+
+
+@pytest.mark.parametrize("N,nc", C.EIGHT_SHARD_CASES)
+def test_eight_shard_cases_see_the_last_iteration_and_the_ghosts(N, nc):
+    G, u, dx, dts = C.eight_shard_input(N, nc)
+    u, want, mutant = C.steps_ref(u, dx, N, G, dts)
+    C.check_rank_slices(u, want, mutant, C.rank_slices(nc, [2, 2, 2]), lambda r, sl: C.steps_ref(u[sl], dx, N, nc, dts)[1], what="eight shards %s" % (G,))
+
+
+def test_sharded_xt_case_sees_the_last_iteration_the_ghosts_and_the_shard_offset():
+    pytest.importorskip("sympy")
+    dim, N, nc, pdims = C.SHARDED_XT_CASE
+    p, o, G, u, dx, dt = C.sharded_xt_input()
+    u, want, mutant = C.xt_ref(o, u, dx, dt, N)
+    slices = C.rank_slices(nc, pdims)
+    offset = lambda sl: [C.XT_ORIGIN[a] + sl[a].start * dx[a] for a in range(dim)]      # noqa: E731
+    C.check_rank_slices(u, want, mutant, slices, lambda r, sl: C.xt_ref(o, u[sl], dx, dt, N, origin=offset(sl))[1], what="x/t + ncp")
+    # a shard that evaluates its terms at the global origin (its offset left out): the whole grid shifted so that the shard's cells sit there
+    sl = slices[1]
+    assert offset(sl) != C.XT_ORIGIN
+    shifted = C.xt_ref(o, u, dx, dt, N, origin=[2 * C.XT_ORIGIN[a] - offset(sl)[a] for a in range(dim)])[1]
+    e = dg_err(shifted[sl], want[sl], u[sl])
+    assert e >= 100 * DG_TOL, e
+
+
+@pytest.mark.parametrize("N,nc,pdims", C.SHARDED_RUN_CASES)
+def test_sharded_run_cases_see_the_reduction(N, nc, pdims):
+    """run() on two shards: three steps; the largest eigenvalue is rank 1's and 1.5 times rank 0's, so a rank 0 that skips the all_reduce takes
+    another step count or ends elsewhere."""
+    G, u, dx, t_end = C.sharded_run_input(N, nc, pdims)
+    slices = C.rank_slices(nc, pdims)
+    lam = [dg_max_eigenvalue(u[sl], 3) for sl in slices]
+    assert lam[1] == dg_max_eigenvalue(u, 3) and lam[1] >= 1.5 * lam[0], lam
+    steps, t, want = C.run_replay(u, dx, N, G, t_end)
+    assert steps == 3 and abs(t - t_end) <= 1e-14 * t_end
+    m_steps, _, mutant = C.run_replay(u, dx, N, G, t_end, n_it=N - 1)
+    assert m_steps == 3
+    C.check_rank_slices(u, want, mutant, slices, lambda r, sl: C.run_replay(u[sl], dx, N, nc, t_end)[2], what="run %s" % (G,))
+    l_steps, _, local = C.run_replay(u, dx, N, G, t_end, lam_of=lambda state: dg_max_eigenvalue(state[slices[0]], 3))
+    assert l_steps != steps or dg_err(local[slices[0]], want[slices[0]], u[slices[0]]) >= 100 * DG_TOL, l_steps

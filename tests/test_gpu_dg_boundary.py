@@ -326,7 +326,7 @@ import os, sys
 sys.path.insert(0, %(root)r)
 import numpy as np, torch, torch.distributed as dist
 from exahype_amd import solvers as exa
-from tests.util import euler_dg_state
+from tests.util import assert_shard_equals_whole_block, euler_dg_state
 rank, world = int(os.environ["RANK"]), int(os.environ["WORLD_SIZE"])
 torch.cuda.set_device(0)
 dist.init_process_group(%(backend)r, rank=rank, world_size=world)
@@ -349,9 +349,17 @@ for k in range(3):
 torch.cuda.synchronize()
 got, want = s.download(), whole.download()[sl]
 err = np.max(np.abs(got - want)) / np.max(np.abs(want))
-assert err <= 1e-13, err
-dist.barrier(); dist.destroy_process_group()
+failed = None
+try:
+    assert err <= 1e-13, err
+    # the same stage-A kernel on shard and block (its name depends on N, n_picard and the variant alone): equal bit for bit
+    assert_shard_equals_whole_block(got, want, u[sl], s, whole, "walls N %%d %%s, rank %%d" %% (N, nc, rank))
+except AssertionError as e:
+    failed = e
+dist.barrier(); dist.destroy_process_group()                    # (leave together: a rank that failed alone would keep the others waiting)
 print("rank", rank, "rel err", err, "bit-equal", np.array_equal(got, want))
+if failed is not None:
+    raise failed
 '''
 
 

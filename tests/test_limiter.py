@@ -71,6 +71,22 @@ def test_limited_step_cases_see_the_last_iteration(dim, N, nc):
     assert_dg_parity(ref, ref, u, _limited_ref(u, mask, dt, dx, N, N - 1), what="limited steps")
 
 
+@pytest.mark.parametrize("dim,N,nc,pdims", C.SHARDED_LIMITER_CASES)
+def test_sharded_limited_step_cases_see_the_last_iteration_and_the_ghosts(dim, N, nc, pdims):
+    """CPU half of tests/test_gpu_distributed.py's limited steps, on every rank's cells: the Picard iteration less is seen, and so is a block
+    that steps alone (periodic in itself: neither ghost traces nor the neighbour's subcell layers)."""
+    G, u, dx, dt, mask = C.sharded_limiter_input(dim, N, nc, pdims)
+    u, want, mutant = C.limited_ref(u, mask, dt, dx, N)
+    C.check_rank_slices(u, want, mutant, C.rank_slices(nc, pdims), lambda r, sl: C.limited_ref(u[sl], mask[sl], dt, dx, N)[1], what="limited %s" % (G,))
+
+
+@pytest.mark.parametrize("N,nc,limited", [c for c in C.SHARDED_SELF_CASES if c[2]])
+def test_sharded_self_limited_step_cases_see_the_last_iteration(N, nc, limited):
+    G, u, dx, dts = C.sharded_self_input(N, nc, limited)
+    u, want, mutant = C.limited_ref(u, C.limiter_mask(G), dts[0], dx, N)
+    C.check_rank_slices(u, want, mutant, C.rank_slices(nc, [1, 1, 1]), what="limited, rccl to self %s" % (G,))
+
+
 @pytest.mark.gpu
 @pytest.mark.parametrize("dim,N,nc", C.LIMITER_CASES)
 def test_limited_step_vs_oracle(dim, N, nc):

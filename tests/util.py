@@ -96,6 +96,25 @@ def assert_dg_parity(got, want, base, mutant=None, tol=DG_TOL, var_axis=-1, what
     return e, em
 
 
+def assert_shard_equals_whole_block(got, whole, base, shard, block, what=""):
+    """A shard's cells against the same cells of the un-sharded block stepped on the same GPU (`shard`, `block`: the two AderDgSolvers).  Stage A
+    is per cell and stage B's arithmetic does not depend on where a neighbour's trace is read from (tests/test_stage_b_chain.py
+    test_traversal_does_not_change_a_bit), so where the same stage-A kernel serves both the results are equal bit for bit; where the
+    selector picks different kernels they agree to DG_TOL of the increment."""
+    a, b = shard.stage_a_kernel_name(), block.stage_a_kernel_name()
+    got, whole = np.asarray(got), np.asarray(whole)
+    same = bool(np.array_equal(got, whole))
+    if os.environ.get("EXA_DG_ERR_LOG"):
+        with open(os.environ["EXA_DG_ERR_LOG"], "a") as f:
+            f.write(json.dumps(dict(test=os.environ.get("PYTEST_CURRENT_TEST", ""), what=what + " == whole block", bit_equal=same,
+                                    err=dg_err(got, whole, base), kernels=[a, b])) + "\n")
+    if a == b:
+        assert same, "%s: shard != whole block, dg_err %.3e (stage A %s)" % (what, dg_err(got, whole, base), a)
+    else:
+        print("%s: stage A of the shard is %s, of the whole block %s" % (what, a, b))
+        assert_dg_parity(got, whole, base, what=what + " against the whole block")
+
+
 def euler_supersonic_state(shape, seed):
     """Admissible Euler state with velocities up to +-2 and sound speed ~1.2: sub- and supersonic nodes, both flow directions, both
     eigenvalue branches |u_n - c| and |u_n + c| as the maximum."""
