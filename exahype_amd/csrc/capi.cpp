@@ -812,7 +812,7 @@ int exa_dg_reconstruct_patches(exa_dg_plan* p, const double* patch_dev, const lo
     if (rc) return rc;
     const int Ns = 2 * p->N - 1;
     return limiter_reconstruct(p->dim, p->N, Ns, p->nv, patch_dev, cells_dev, n, u_dev,
-                               static_cast<const double*>(p->ops.lim) + (size_t)p->N * Ns, (hipStream_t)stream);
+                               static_cast<const double*>(p->ops.lim) + (size_t)p->N * Ns, 1, (hipStream_t)stream);
 }
 
 /* ---- patches with halo 2: what the second-order patch update (EXA_FV_MUSCL_HANCOCK) reads ---- */
@@ -852,8 +852,8 @@ int exa_lim_reconstruct_patches_halo(exa_dg_plan* p, const double* patch_dev, co
     rc = lim_tables(p);
     if (rc) return rc;
     const int Ns = 2 * p->N - 1;
-    return limiter_reconstruct_halo(p->dim, p->N, Ns, p->nv, patch_dev, cells_dev, n, u_dev, static_cast<const double*>(p->ops.lim) + (size_t)p->N * Ns, halo,
-                                    (hipStream_t)stream);
+    return limiter_reconstruct(p->dim, p->N, Ns, p->nv, patch_dev, cells_dev, n, u_dev, static_cast<const double*>(p->ops.lim) + (size_t)p->N * Ns, halo,
+                               (hipStream_t)stream);
 }
 
 // the registered term set of the plan if it carries its own criterion (EXA_PDE_FLAG_ADMISSIBLE), else null

@@ -30,13 +30,11 @@ int limiter_project(int dim, int N, int Ns, int nv, const long* nc, const double
 int limiter_face_layers(int dim, int N, int Ns, int nv, const long* nc, const double* u, int a, int side, const double* need,
                         double* out, const double* Pdev, hipStream_t s);
 int limiter_reconstruct(int dim, int N, int Ns, int nv, const double* patch, const long* cells, long n, double* u,
-                        const double* Rdev, hipStream_t s);
+                        const double* Rdev, int halo, hipStream_t s);        // halo: the patches', 1 | 2
 // patches with halo 2 (the second-order patch update): face halos two layers deep, edge entries from the diagonal cells; kinds (host, null: all
-// periodic) / data (device, [2 dim][nv]): FV_FACE_* of the domain faces and their signs / states.  limiter_reconstruct_halo: halo 1 | 2
+// periodic) / data (device, [2 dim][nv]): FV_FACE_* of the domain faces and their signs / states
 int limiter_project_halo2(int dim, int N, int nv, const long* nc, const double* u, const long* cells, long n, double* patch,
                           const double* Pdev, const int* kinds, const double* data, hipStream_t s);
-int limiter_reconstruct_halo(int dim, int N, int Ns, int nv, const double* patch, const long* cells, long n, double* u,
-                             const double* Rdev, int halo, hipStream_t s);
 // a-posteriori detection: u^n -> u_old (may be null) + bounds[cell][4]; candidate + bounds (+ neighbour blocks' bounds) -> mask bytes
 int limiter_snapshot(int dim, int N, int nv, long ncells, const double* u, double* u_old, double* bounds, hipStream_t s);
 int limiter_detect(int dim, int N, int nv, const long* nc, const double* u, const double* bounds, const LimGhosts* ghosts, const int* kinds,

@@ -12,7 +12,7 @@ from tests.util import euler_dg_state, euler_scaled_state, euler_supersonic_stat
 
 LD = np.longdouble
 KERNEL_CASES = [(dim, N) for dim in (2, 3) for N in L.ORDERS]
-FORMS = ("all_variables", "per_variable")                  # five-variable systems: default | EXA_LIM_PER_VARIABLE=1
+FORMS = ("all_variables", "per_variable")                  # five-variable systems: NV = 5, one round (default) | NV = 1, five rounds (EXA_LIM_PER_VARIABLE=1)
 GRIDS = {2: [(1, 3), (3, 2), (2, 3), (3, 1)], 3: [(1, 2, 3), (3, 1, 2), (2, 3, 1)]}
 STATE_KINDS = ("supersonic", "scaled_2^20", "plain")
 SENTINEL = -8.765432101234567e+250                          # no result comes near it; compared bit for bit

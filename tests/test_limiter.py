@@ -113,9 +113,9 @@ def test_limited_step_vs_oracle(dim, N, nc):
 @pytest.mark.gpu
 @pytest.mark.parametrize("dim,N,nc", [(3, 8, (2, 1, 2)), (2, 4, (3, 2)), (3, 3, (2, 2, 2))])
 def test_all_variables_kernels_equal_the_per_variable_kernels(dim, N, nc, monkeypatch):
-    """Five-variable systems take the all-variables projection / reconstruction kernels (AoS runs, one pass over the patch);
-    EXA_LIM_PER_VARIABLE=1 sends them through the per-variable kernels every other variable count uses.  Same summation
-    order: the limited step must come out bit for bit the same."""
+    """Five-variable systems take the projection / reconstruction kernels with all five variables in a lane (NV = 5: AoS runs, one
+    round over the patch); EXA_LIM_PER_VARIABLE=1 sends them through the same kernels one variable at a time (NV = 1, five rounds),
+    the instantiation every other variable count uses.  Same summation order: the limited step must come out bit for bit the same."""
     from exahype_amd import solvers as exa
     u = euler_dg_state(tuple(nc) + (N,) * dim, seed=77)
     dx = [1.0 / nc[0]] * dim

@@ -1,7 +1,7 @@
 """Every limiter glue kernel of exahype_amd/csrc/limiter.hip against the long-double reference (oracle/limiter_reference.py), through the C
 entry points: projection onto the FV patch with halo (periodic and with ghost layers), the face layers of a block face, the
-reconstruction -- at every order N = 2 .. 8 in 2-D and 3-D, in both kernel forms of five-variable systems (all variables at once |
-EXA_LIM_PER_VARIABLE=1) and through the per-variable kernels at one and two variables.
+reconstruction -- at every order N = 2 .. 8 in 2-D and 3-D, in both instantiations that serve five-variable systems (NV = 5: all
+variables in a lane, one round | NV = 1: one variable at a time, EXA_LIM_PER_VARIABLE=1) and in the NV = 1 instantiation at one and two variables.
 
 Operators: exa_lim_operators against tests/golden/limiter_operators_hp.json (mpmath, 40 digits) within 8 * 2^-53 * cond(K).
 Kernels: against the reference built from the DEVICE's own P, R applied in long double, element by element within
@@ -160,7 +160,8 @@ def test_projection_whole_patch(dim, N, form, monkeypatch):
 @pytest.mark.parametrize("nv", [1, 2])
 @pytest.mark.parametrize("dim,N", K.KERNEL_CASES)
 def test_other_variable_counts(dim, N, nv):
-    """The per-variable kernels at their own strides: projection (whole patch), face layers and reconstruction."""
+    """The NV = 1 instantiation at the strides of one and two variables (one round | two): projection (whole patch), face layers and
+    reconstruction."""
     worst = [0.0, 0.0, 0.0]
     for g, (nc, kind, u) in enumerate(K.inputs(dim, N, nv)):
         s = _solver(dim, N, nc, nv)
@@ -173,7 +174,7 @@ def test_other_variable_counts(dim, N, nv):
                 worst[1] = max(worst[1], _check_face_layers(s, u, d, side, P, None))
         worst[2] = max(worst[2], _check_reconstruction(s, R, u, seed=300 * N + g))
     for kind, w in zip(("projection", "face_layers", "reconstruction"), worst):
-        log_limiter_measurement(kind, dim=dim, N=N, form="single" if kind == "face_layers" else "per_variable", nv=nv, ratio=w)
+        log_limiter_measurement(kind, dim=dim, N=N, form="per_variable", nv=nv, ratio=w)
 
 
 @pytest.mark.parametrize("form", K.FORMS)
@@ -220,11 +221,15 @@ def _check_face_layers(s, u, d, side, P, need):
     return K.worst_ratio(got[done], ref[done], bound[done]) if done.any() else 0.0
 
 
-@pytest.mark.parametrize("dim,N", K.KERNEL_CASES)
-def test_face_layers(dim, N, monkeypatch):
-    """Every (d, side): all cells (need = NULL), then a mask of mixed zeros and non-zeros over a sentinel-filled output.  Then the layers as
-    ghost buffers of the opposite faces of the same block: the patches must equal the periodic ones bit for bit (the face-layer kernel and
-    the halo part of both projection kernels compute the same sums in the same order)."""
+# (the cases of the default form keep the ids they had when the face-layer kernel had one form: [dim-N])
+@pytest.mark.parametrize("dim,N,form", [(dim, N, form) for form in K.FORMS for dim, N in K.KERNEL_CASES],
+                         ids=["%d-%d%s" % (dim, N, "" if form == K.FORMS[0] else "-" + form) for form in K.FORMS for dim, N in K.KERNEL_CASES])
+def test_face_layers(dim, N, form, monkeypatch):
+    """Every (d, side): all cells (need = NULL), then a mask of mixed zeros and non-zeros over a sentinel-filled output.  The layers of the
+    two instantiations of the face-layer kernel are bit-equal.  Then the layers as ghost buffers of the opposite faces of the same block:
+    the patches must equal the periodic ones bit for bit (the face-layer kernel and the halo part of the projection kernel compute the
+    same sums in the same order), the projection in either form."""
+    other = K.FORMS[1 - K.FORMS.index(form)]
     worst = 0.0
     for g, (nc, kind, u) in enumerate(K.inputs(dim, N)):
         s = _solver(dim, N, nc)
@@ -234,19 +239,24 @@ def test_face_layers(dim, N, monkeypatch):
         for d in range(dim):
             nt = int(np.prod(nc)) // nc[d]
             for side in (0, 1):
+                _set_form(monkeypatch, form)
                 worst = max(worst, _check_face_layers(s, u, d, side, P, None))
                 need = rng.choice([0.0, 1.0, -2.5, 1e-300], size=nt)
                 if nt > 1:
                     need[rng.integers(nt)] = 0.0
                     need[(np.flatnonzero(need == 0)[0] + 1) % nt] = 3.0
                 worst = max(worst, _check_face_layers(s, u, d, side, P, need))
-                layers[(d, 1 - side)] = _face_layers(s, u, d, side)            # what the block across face (d, 1 - side) would send
+                mine = [_face_layers(s, u, d, side), _face_layers(s, u, d, side, need)]
+                layers[(d, 1 - side)] = mine[0]                                # what the block across face (d, 1 - side) would send
+                _set_form(monkeypatch, other)
+                for got, nd in zip(mine, (None, need)):
+                    assert np.array_equal(_bits(got), _bits(_face_layers(s, u, d, side, nd))), (nc, d, side, form, other)
         cells = K.cell_list(int(np.prod(nc)), seed=600 * N + g)
-        for form in K.FORMS:
-            _set_form(monkeypatch, form)
+        for project_form in K.FORMS:
+            _set_form(monkeypatch, project_form)
             periodic, ghosted = _project(s, u, cells), _project(s, u, cells, layers)
-            assert np.array_equal(_bits(periodic), _bits(ghosted)), (nc, form)
-    log_limiter_measurement("face_layers", dim=dim, N=N, form="single", nv=5, ratio=worst)
+            assert np.array_equal(_bits(periodic), _bits(ghosted)), (nc, form, project_form)
+    log_limiter_measurement("face_layers", dim=dim, N=N, form=form, nv=5, ratio=worst)
 
 
 def _check_reconstruction(s, R, u0, seed):
