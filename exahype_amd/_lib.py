@@ -11,7 +11,8 @@ LIB_PATH = os.path.join(HERE, "lib", "libexahype_hip.so")
 
 PDE_EULER_REF2D, PDE_EULER, PDE_ADVECTION = 0, 1, 2
 FV_FAITHFUL, FV_RUSANOV, FV_MUSCL_HANCOCK = 0, 1, 2         # include/exahype_hip.h EXA_FV_*
-FV_FACE_PERIODIC, FV_FACE_STATE, FV_FACE_MIRROR = 0, 1, 2      # include/exahype_hip.h EXA_FV_FACE_*
+FV_STREAM_NEVER, FV_STREAM_IF_NEEDED, FV_STREAM_ALWAYS = 0, 1, 2      # include/exahype_hip.h EXA_FV_STREAM_* (exa_fv_plan_create_streamed)
+FV_FACE_PERIODIC, FV_FACE_STATE, FV_FACE_MIRROR = 0, 1, 2     # include/exahype_hip.h EXA_FV_FACE_*
 PDE_FLAG_XT, PDE_FLAG_NCP, PDE_FLAG_ADMISSIBLE, PDE_FLAG_CONSERVATIVE, PDE_FLAG_MUSCL_HANCOCK = 1, 2, 4, 8, 16      # EXA_PDE_FLAG_*
 PDE_FLAG_MUSCL_TERMS = 32
 
@@ -26,6 +27,8 @@ SIGNATURES = {
     "exa_pde_eval_device": (C.c_int, [C.c_int, C.c_int, C.c_long, C.c_int, _vp, _vp, _vp, _vp]),
     "exa_pde_eval_device_at": (C.c_int, [C.c_int, C.c_int, C.c_long, C.c_int, _vp, _vp, C.c_double, _vp, _vp, _vp]),
     "exa_fv_plan_create": (C.c_int, [C.c_int] * 7 + [C.c_long, C.c_int, C.POINTER(_vp)]),
+    "exa_fv_plan_create_streamed": (C.c_int, [C.c_int] * 7 + [C.c_long, C.c_int, C.c_int, C.POINTER(_vp)]),
+    "exa_fv_plan_is_streamed": (C.c_int, [_vp]),
     "exa_fv_plan_destroy": (C.c_int, [_vp]),
     "exa_fv_q_count": (C.c_long, [_vp]),
     "exa_fv_time_step_host": (C.c_int, [_vp, _vp, C.c_double, C.c_double]),

@@ -56,6 +56,8 @@ struct UserPde {
     int (*fvm)(int, int, int, int, int, long, double*, double, double, const long*, void*, double*);
     // ... and of its grid step on halo-less arrays (exa_user_fv_muscl_grid_launch); null in a library built before that entry existed
     int (*fvmg)(int, int, int, int, long, const double*, double*, double, double, const void*, void*);
+    // ... and of the plane-streaming form of the 3-D update (exa_user_fv_muscl_stream_launch); null in a library built before that entry existed
+    int (*fvms)(int, int, int, int, long, double*, double, double, const long*, void*, double*);
 };
 static std::vector<UserPde> g_user;
 
@@ -68,6 +70,11 @@ int user_fv_muscl_launch(int pde, int dim, int P, int H, int n_real, int n_aux, 
                          hipStream_t s, double* out) {
     if (pde - 100 >= (int)g_user.size() || !g_user[pde - 100].fvm) { set_error("pde %d carries no MUSCL-Hancock kernel", pde); return -1; }
     return g_user[pde - 100].fvm(dim, P, H, n_real, n_aux, n_patches, Q, dt, h, slot, (void*)s, out);
+}
+int user_fv_muscl_stream_launch(int pde, int P, int H, int n_real, int n_aux, long n_patches, double* Q, double dt, double h, const long* slot,
+                                hipStream_t s, double* out) {
+    if (pde - 100 >= (int)g_user.size() || !g_user[pde - 100].fvms) { set_error("pde %d carries no streamed MUSCL-Hancock kernel", pde); return -1; }
+    return g_user[pde - 100].fvms(P, H, n_real, n_aux, n_patches, Q, dt, h, slot, (void*)s, out);
 }
 int user_fv_muscl_grid_launch(int pde, int dim, int P, int n_real, int n_aux, long n_patches, const double* Q, double* out, double dt, double h,
                               const FvMusclGrid* grid, hipStream_t s) {
@@ -107,6 +114,7 @@ using namespace exa;
 struct exa_fv_plan {
     int device, mode, dim, P, H, n_real, n_aux, pde;
     long n_patches, count;
+    int streamed;          // EXA_FV_MUSCL_HANCOCK, 3-D: the plane-streaming kernel serves the plan (exa_fv_plan_create_streamed)
 };
 
 struct exa_dg_plan {
@@ -193,6 +201,7 @@ int exa_register_pde(const char* library_path, int* pde_id) {
             return EXA_ERR_INVALID;
         }
         u.fvmg = (decltype(u.fvmg))dlsym(h, "exa_user_fv_muscl_grid_launch");      // (optional: older cached builds have none)
+        u.fvms = (decltype(u.fvms))dlsym(h, "exa_user_fv_muscl_stream_launch");    // (optional likewise)
     }
     g_user.push_back(u);
     *pde_id = 100 + (int)g_user.size() - 1;
@@ -226,8 +235,9 @@ int exa_pde_eval_device_at(int pde, int normal, long n, int stride, const double
 
 /* ---- FV ---------------------------------------------------------------------- */
 
-int exa_fv_plan_create(int device, int mode, int dim, int patch_size, int halo_size, int n_real, int n_aux,
-                       long n_patches, int pde, exa_fv_plan** plan) {
+// both plan entries; stream_planes: EXA_FV_STREAM_* (exa_fv_plan_create: NEVER)
+static int fv_plan_create(int device, int mode, int dim, int patch_size, int halo_size, int n_real, int n_aux, long n_patches, int pde, int stream_planes,
+                          exa_fv_plan** plan) {
     if (!plan) { set_error("exa_fv_plan_create: NULL plan"); return EXA_ERR_INVALID; }
     *plan = nullptr;
     // same viability rule as the reference's KernelBuilder (exahype/KernelBuilder.py:41-48) ...
@@ -236,6 +246,19 @@ int exa_fv_plan_create(int device, int mode, int dim, int patch_size, int halo_s
     if (halo_size < 1) { set_error("the Rusanov stencil reads one halo layer: halo_size must be >= 1"); return EXA_ERR_INVALID; }
     if (mode != EXA_FV_FAITHFUL && mode != EXA_FV_RUSANOV && mode != EXA_FV_MUSCL_HANCOCK) { set_error("unknown FV mode %d", mode); return EXA_ERR_INVALID; }
     if (mode == EXA_FV_MUSCL_HANCOCK && halo_size < 2) { set_error("MUSCL-Hancock reads two halo layers: halo_size must be >= 2"); return EXA_ERR_INVALID; }
+    if (stream_planes != EXA_FV_STREAM_NEVER && stream_planes != EXA_FV_STREAM_IF_NEEDED && stream_planes != EXA_FV_STREAM_ALWAYS) {
+        set_error("exa_fv_plan_create_streamed: unknown stream_planes %d (EXA_FV_STREAM_NEVER / _IF_NEEDED / _ALWAYS)", stream_planes);
+        return EXA_ERR_INVALID;
+    }
+    if (stream_planes != EXA_FV_STREAM_NEVER && mode != EXA_FV_MUSCL_HANCOCK) {
+        set_error("exa_fv_plan_create_streamed: plane streaming is a form of EXA_FV_MUSCL_HANCOCK; mode %d takes stream_planes = EXA_FV_STREAM_NEVER", mode);
+        return EXA_ERR_INVALID;
+    }
+    if (stream_planes == EXA_FV_STREAM_ALWAYS && dim != 3) {
+        set_error("exa_fv_plan_create_streamed: EXA_FV_STREAM_ALWAYS in %d-D -- the plane-streaming kernel is 3-D only (every 2-D patch up to 32^2 has a "
+                  "resident plan)", dim);
+        return EXA_ERR_INVALID;
+    }
     if (n_real < 1 || n_real > 8 || n_aux < 0 || n_patches < 0) { set_error("n_real must be 1..8, n_aux >= 0, n_patches >= 0"); return EXA_ERR_INVALID; }
     if (pde == EXA_PDE_EULER_REF2D && (dim != 2 || n_real < 4)) { set_error("EULER_REF2D is the reference's 2-D term set (n_real >= 4)"); return EXA_ERR_INVALID; }
     if (pde == EXA_PDE_EULER && n_real < 5) { set_error("EULER needs n_real >= 5"); return EXA_ERR_INVALID; }
@@ -243,6 +266,7 @@ int exa_fv_plan_create(int device, int mode, int dim, int patch_size, int halo_s
         if (pde - 100 >= (int)g_user.size()) { set_error("pde %d is not registered", pde); return EXA_ERR_INVALID; }
         if (n_real < g_user[pde - 100].nv) { set_error("pde %d evolves %d variables; n_real = %d", pde, g_user[pde - 100].nv, n_real); return EXA_ERR_INVALID; }
     } else if (pde < 0 || pde > 2) { set_error("unknown pde %d", pde); return EXA_ERR_INVALID; }
+    int streamed = 0;
     if (mode == EXA_FV_MUSCL_HANCOCK) {
         if (pde == EXA_PDE_EULER_REF2D) {
             set_error("EXA_FV_MUSCL_HANCOCK: EULER_REF2D is the reference's quirk set (F[4] is never written); use EXA_PDE_EULER");
@@ -253,8 +277,24 @@ int exa_fv_plan_create(int device, int mode, int dim, int patch_size, int halo_s
             return EXA_ERR_INVALID;
         }
         FvMusclPlan pl;
-        if (patch_size > 1024 || !fv_muscl_plan(dim, patch_size, n_real, n_real + n_aux, &pl)) {
-            if (patch_size > 1024) pl.lds = (size_t)-1;
+        const bool resident = patch_size <= 1024 && fv_muscl_plan(dim, patch_size, n_real, n_real + n_aux, &pl);
+        if (patch_size > 1024) pl.lds = (size_t)-1;
+        if (dim == 3 && (stream_planes == EXA_FV_STREAM_ALWAYS || (stream_planes == EXA_FV_STREAM_IF_NEEDED && !resident))) {
+            FvMusclPlan ps;
+            if (patch_size > 1024 || !fv_muscl_stream_plan(patch_size, n_real, n_real + n_aux, &ps)) {
+                if (patch_size > 1024) ps.lds = (size_t)-1;
+                set_error("EXA_FV_MUSCL_HANCOCK: a patch of %d^3 volumes with %d + %d variables needs %zu bytes of LDS with the whole window resident and "
+                          "%zu bytes plane by plane (five window planes, three predictor planes), %zu bytes are available", patch_size, n_real, n_aux,
+                          pl.lds, ps.lds, FV_MUSCL_LDS_AVAILABLE);
+                return EXA_ERR_INVALID;
+            }
+            if (pde >= 100 && !g_user[pde - 100].fvms) {
+                set_error("EXA_FV_MUSCL_HANCOCK: pde %d: its side library exports no exa_user_fv_muscl_stream_launch (built before the plane-streaming "
+                          "kernel existed); rebuild the term set (SympyPDE(..., muscl_hancock=True).build(force=True))", pde);
+                return EXA_ERR_INVALID;
+            }
+            streamed = 1;
+        } else if (!resident) {
             set_error("EXA_FV_MUSCL_HANCOCK: a patch of %d^%d volumes with %d + %d variables needs %zu bytes of LDS (window and predictor), %zu bytes are "
                       "available", patch_size, dim, n_real, n_aux, pl.lds, FV_MUSCL_LDS_AVAILABLE);
             return EXA_ERR_INVALID;
@@ -269,9 +309,22 @@ int exa_fv_plan_create(int device, int mode, int dim, int patch_size, int halo_s
     p->device = device; p->mode = mode; p->dim = dim; p->P = patch_size; p->H = halo_size;
     p->n_real = n_real; p->n_aux = n_aux; p->pde = pde; p->n_patches = n_patches;
     p->count = n_patches * lpow(patch_size + 2 * halo_size, dim) * (n_real + n_aux);
+    p->streamed = streamed;
     *plan = p;
     return EXA_OK;
 }
+
+int exa_fv_plan_create(int device, int mode, int dim, int patch_size, int halo_size, int n_real, int n_aux,
+                       long n_patches, int pde, exa_fv_plan** plan) {
+    return fv_plan_create(device, mode, dim, patch_size, halo_size, n_real, n_aux, n_patches, pde, EXA_FV_STREAM_NEVER, plan);
+}
+
+int exa_fv_plan_create_streamed(int device, int mode, int dim, int patch_size, int halo_size, int n_real, int n_aux, long n_patches, int pde,
+                                int stream_planes, exa_fv_plan** plan) {
+    return fv_plan_create(device, mode, dim, patch_size, halo_size, n_real, n_aux, n_patches, pde, stream_planes, plan);
+}
+
+int exa_fv_plan_is_streamed(const exa_fv_plan* plan) { return plan && plan->streamed ? 1 : 0; }
 
 int exa_fv_plan_destroy(exa_fv_plan* plan) { delete plan; return EXA_OK; }
 
@@ -279,6 +332,8 @@ long exa_fv_q_count(const exa_fv_plan* plan) { return plan ? plan->count : 0; }
 
 // the second-order update of a plan in mode EXA_FV_MUSCL_HANCOCK (its term sets see the state alone: no centres, no time)
 static int fv_muscl(exa_fv_plan* p, double* Q_dev, double dt, double h, const long* slot_dev, void* stream, double* out_dev) {
+    if (p->streamed)
+        return fv_muscl_stream_launch(p->P, p->H, p->n_real, p->n_aux, p->n_patches, p->pde, Q_dev, dt, h, slot_dev, (hipStream_t)stream, out_dev);
     return fv_muscl_launch(p->dim, p->P, p->H, p->n_real, p->n_aux, p->n_patches, p->pde, Q_dev, dt, h, slot_dev, (hipStream_t)stream, out_dev);
 }
 
@@ -384,6 +439,11 @@ int exa_fv_grid_step_muscl_device(exa_fv_plan* p, const double* Q_dev, double* Q
     if (p->mode != EXA_FV_MUSCL_HANCOCK) {
         set_error("%s: the plan's mode is %d, this entry serves EXA_FV_MUSCL_HANCOCK plans; exa_fv_grid_step_device[_bc] is the grid step of the "
                   "other modes", who, p->mode);
+        return EXA_ERR_INVALID;
+    }
+    if (p->streamed) {
+        set_error("%s: the plan streams its patches plane by plane (exa_fv_plan_create_streamed); the one-launch gather is not built for that form -- "
+                  "use the two-pass form: fill the halos of the array with halo and call exa_fv_time_step_device", who);
         return EXA_ERR_INVALID;
     }
     if (p->P < 2) {

@@ -27,6 +27,11 @@
 // fv_muscl_grid_kernel (further down) is the GRID form on halo-less arrays: the same plan and the same two phases (fv_muscl_predict,
 // fv_muscl_correct -- the device functions both kernels call, so the results are bit-identical), another staging -- the window is gathered from the
 // patch, its face neighbours and its diagonal neighbours -- and the next step's CFL scan reduced from the values phase 2 stores.
+//
+// fv_muscl_stream_kernel is the PLANE-STREAMING form for 3-D patches whose window does not fit (P >= 10 at five variables; up to P = 19): a ring of
+// five or six window planes and three predictor planes instead of the whole window, one walk along axis 0.  The loop bodies of both phases are the
+// per-volume functions fv_muscl_predict_volume / fv_muscl_correct_volume, which all three kernels call: a volume's neighbours are described by their
+// distances (FvMusclNbr), uniform strides in the resident and the grid kernel, ring-slot distances along axis 0 in the streamed one.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -53,11 +58,20 @@ __device__ __forceinline__ double fv_minmod(double a, double b) {
     return 0.0;                                                   // opposite signs, a zero, a NaN
 }
 
-// slopes of the evolved variables of the volume at q (window image) along the axis whose neighbours lie `st` doubles away
-__device__ __forceinline__ void fv_muscl_slope(const double* q, int st, int m, double (&s)[FVM_MAXV]) {
+// slopes of the evolved variables of the volume at q along the axis whose minus neighbour stands sm doubles below it, the plus neighbour sp above
+__device__ __forceinline__ void fv_muscl_slope(const double* q, int sm, int sp, int m, double (&s)[FVM_MAXV]) {
 #pragma unroll
-    for (int v = 0; v < FVM_MAXV; v++) s[v] = v < m ? fv_minmod(q[v] - q[v - st], q[v + st] - q[v]) : 0.0;
+    for (int v = 0; v < FVM_MAXV; v++) s[v] = v < m ? fv_minmod(q[v] - q[v - sm], q[v + sp] - q[v]) : 0.0;
 }
+
+// where a volume finds its neighbours along every axis e, as distances in doubles: the window entry at -1 stands qm[e] below the volume's own, the
+// one at -2 qmm[e] below THAT; qp[e] / qpp[e] likewise upwards; the predictor's increments at -1 / +1 stand dm[e] below / dp[e] above.  The resident
+// and the grid kernel fill all of them with the axis' stride; in the streamed kernel the axis-0 neighbours stand in other ring slots, at distances
+// of their own (of either sign)
+struct FvMusclNbr {
+    int qmm[3], qm[3], qp[3], qpp[3];
+    int dm[3], dp[3];
+};
 
 // Rusanov flux of (wL, wR) along D
 template <class PDE, int D>
@@ -91,6 +105,102 @@ template <int DIM> __device__ __forceinline__ void fv_muscl_strides(int T, int D
     else { tst[0] = T; tst[1] = 1; tst[2] = 0; dst[0] = D; dst[1] = 1; dst[2] = 0; }
 }
 
+// the predictor of ONE plus-shape volume at q (neighbours nb.qm, nb.qp) -> dl[0 .. m); hr = r / 2
+template <int DIM, class PDE>
+__device__ __forceinline__ void fv_muscl_predict_volume(const double* q, const FvMusclNbr& nb, double* dl, int m, double hr, [[maybe_unused]] double dt) {
+    double qc[FVM_MAXV], sum[FVM_MAXV];
+#pragma unroll
+    for (int v = 0; v < FVM_MAXV; v++) { qc[v] = v < m ? q[v] : 0.0; sum[v] = 0.0; }
+    static_for_muscl<0, DIM>([&](auto ee) {
+        constexpr int e = decltype(ee)::value;
+        double s[FVM_MAXV], wp[FVM_MAXV], wm[FVM_MAXV], fp[FVM_MAXV], fm[FVM_MAXV];
+        fv_muscl_slope(q, nb.qm[e], nb.qp[e], m, s);
+#pragma unroll
+        for (int v = 0; v < FVM_MAXV; v++) { wp[v] = qc[v] + 0.5 * s[v]; wm[v] = qc[v] - 0.5 * s[v]; fp[v] = 0.0; fm[v] = 0.0; }
+        PDE::flux_rt(wp, e, fp);
+        PDE::flux_rt(wm, e, fm);
+#pragma unroll
+        for (int v = 0; v < FVM_MAXV; v++) sum[v] = e == 0 ? fp[v] - fm[v] : sum[v] + (fp[v] - fm[v]);
+        if constexpr (pde_has_ncp<PDE>::value) {                  // + B_e(Q_c) s_e(c)
+            double nc[FVM_MAXV];
+#pragma unroll
+            for (int v = 0; v < FVM_MAXV; v++) nc[v] = 0.0;
+            PDE::ncp(qc, s, e, nc);
+#pragma unroll
+            for (int v = 0; v < FVM_MAXV; v++) sum[v] += nc[v];
+        }
+    });
+    if constexpr (pde_has_source<PDE>::value) {                   // + (dt/2) S(Q_c)
+        double Sq[FVM_MAXV];
+#pragma unroll
+        for (int v = 0; v < FVM_MAXV; v++) Sq[v] = 0.0;
+        PDE::source(qc, Sq);
+        const double hdt = 0.5 * dt;
+#pragma unroll
+        for (int v = 0; v < FVM_MAXV; v++)
+            if (v < m) dl[v] = -hr * sum[v] + hdt * Sq[v];
+    } else {
+#pragma unroll
+        for (int v = 0; v < FVM_MAXV; v++)
+            if (v < m) dl[v] = -hr * sum[v];
+    }
+}
+
+// the corrector of ONE interior volume at q with its predictor increments at dl.  Both sides of a face evaluate fv_muscl_face on the same two states.
+// store(updated) is called once at the end and writes the volume where its kernel keeps it: updated(v) is the new value of evolved variable v < m
+template <int DIM, class PDE, class Store>
+__device__ __forceinline__ void fv_muscl_correct_volume(const double* q, const double* dl, const FvMusclNbr& nb, int m, double r, [[maybe_unused]] double dt,
+                                                        Store&& store) {
+    double qc[FVM_MAXV], dC[FVM_MAXV], acc[FVM_MAXV];
+#pragma unroll
+    for (int v = 0; v < FVM_MAXV; v++) { qc[v] = v < m ? q[v] : 0.0; dC[v] = v < m ? dl[v] : 0.0; acc[v] = 0.0; }
+    [[maybe_unused]] double qh[FVM_MAXV];                         // the half-step state Q_c + delta_c, where the volume's own terms are taken
+    if constexpr (pde_has_ncp<PDE>::value || pde_has_source<PDE>::value) {
+#pragma unroll
+        for (int v = 0; v < FVM_MAXV; v++) qh[v] = qc[v] + dC[v];
+    }
+    static_for_muscl<0, DIM>([&](auto dd) {
+        constexpr int d = decltype(dd)::value;
+        const int qmm = nb.qmm[d], qm = nb.qm[d], qp = nb.qp[d], qpp = nb.qpp[d], dm = nb.dm[d], dp = nb.dp[d];
+        double sC[FVM_MAXV], sN[FVM_MAXV], wCp[FVM_MAXV], wCm[FVM_MAXV], wN[FVM_MAXV], Fp[FVM_MAXV], Fm[FVM_MAXV];
+        fv_muscl_slope(q, qm, qp, m, sC);
+#pragma unroll
+        for (int v = 0; v < FVM_MAXV; v++) { wCp[v] = (qc[v] + 0.5 * sC[v]) + dC[v]; wCm[v] = (qc[v] - 0.5 * sC[v]) + dC[v]; }
+        fv_muscl_slope(q + qp, qp, qpp, m, sN);                             // the plus-side neighbour's minus state
+#pragma unroll
+        for (int v = 0; v < FVM_MAXV; v++) wN[v] = v < m ? (q[qp + v] - 0.5 * sN[v]) + dl[dp + v] : 0.0;
+        fv_muscl_face<PDE, d>(wCp, wN, m, Fp);
+        [[maybe_unused]] double Dp[FVM_MAXV], Dm[FVM_MAXV];
+        if constexpr (pde_has_ncp<PDE>::value) fv_muscl_jump<PDE, d>(wCp, wN, m, Dp);
+        fv_muscl_slope(q - qm, qmm, qm, m, sN);                             // the minus-side neighbour's plus state
+#pragma unroll
+        for (int v = 0; v < FVM_MAXV; v++) wN[v] = v < m ? (q[v - qm] + 0.5 * sN[v]) + dl[v - dm] : 0.0;
+        fv_muscl_face<PDE, d>(wN, wCm, m, Fm);
+#pragma unroll
+        for (int v = 0; v < FVM_MAXV; v++) acc[v] = d == 0 ? Fp[v] - Fm[v] : acc[v] + (Fp[v] - Fm[v]);
+        if constexpr (pde_has_ncp<PDE>::value) {                  // + (D_{c+1/2} + D_{c-1/2}) / 2 + B_d(Q_c + delta_c) s_d(c)
+            double Bs[FVM_MAXV];
+            fv_muscl_jump<PDE, d>(wN, wCm, m, Dm);
+#pragma unroll
+            for (int v = 0; v < FVM_MAXV; v++) Bs[v] = 0.0;
+            PDE::ncp(qh, sC, d, Bs);
+#pragma unroll
+            for (int v = 0; v < FVM_MAXV; v++)
+                if (v < m) acc[v] += (0.5 * Dp[v] + 0.5 * Dm[v]) + Bs[v];
+        }
+    });
+    [[maybe_unused]] double Sq[FVM_MAXV];                         // S(Q_c + delta_c): the source at the half-step state
+    if constexpr (pde_has_source<PDE>::value) {
+#pragma unroll
+        for (int v = 0; v < FVM_MAXV; v++) Sq[v] = 0.0;
+        PDE::source(qh, Sq);
+    }
+    store([&](int v) -> double {
+        if constexpr (pde_has_source<PDE>::value) return (qc[v] - r * acc[v]) + dt * Sq[v];
+        else return qc[v] - r * acc[v];
+    });
+}
+
 // phase 1 of a workgroup whose `np` windows stand in img: delta of every plus-shape volume (box coordinates 0 .. P + 1, at most one of them
 // outside 1 .. P) -> del
 template <int DIM, class PDE, int NT>
@@ -113,43 +223,10 @@ __device__ __forceinline__ void fv_muscl_predict(const double* img, double* del,
         for (int a = 0; a < DIM; a++) { outside += (co[a] < 1 || co[a] > P) ? 1 : 0; tc += (co[a] + 1) * tst[a]; }
         if (outside > 1) continue;
         const double* q = img + ((long)pp * tvol + tc) * V;
-        double qc[FVM_MAXV], sum[FVM_MAXV];
+        FvMusclNbr nb;
 #pragma unroll
-        for (int v = 0; v < FVM_MAXV; v++) { qc[v] = v < m ? q[v] : 0.0; sum[v] = 0.0; }
-        static_for_muscl<0, DIM>([&](auto ee) {
-            constexpr int e = decltype(ee)::value;
-            double s[FVM_MAXV], wp[FVM_MAXV], wm[FVM_MAXV], fp[FVM_MAXV], fm[FVM_MAXV];
-            fv_muscl_slope(q, tst[e] * V, m, s);
-#pragma unroll
-            for (int v = 0; v < FVM_MAXV; v++) { wp[v] = qc[v] + 0.5 * s[v]; wm[v] = qc[v] - 0.5 * s[v]; fp[v] = 0.0; fm[v] = 0.0; }
-            PDE::flux_rt(wp, e, fp);
-            PDE::flux_rt(wm, e, fm);
-#pragma unroll
-            for (int v = 0; v < FVM_MAXV; v++) sum[v] = e == 0 ? fp[v] - fm[v] : sum[v] + (fp[v] - fm[v]);
-            if constexpr (pde_has_ncp<PDE>::value) {              // + B_e(Q_c) s_e(c)
-                double nc[FVM_MAXV];
-#pragma unroll
-                for (int v = 0; v < FVM_MAXV; v++) nc[v] = 0.0;
-                PDE::ncp(qc, s, e, nc);
-#pragma unroll
-                for (int v = 0; v < FVM_MAXV; v++) sum[v] += nc[v];
-            }
-        });
-        double* dl = del + ((long)pp * dvol + dc) * m;
-        if constexpr (pde_has_source<PDE>::value) {               // + (dt/2) S(Q_c)
-            double Sq[FVM_MAXV];
-#pragma unroll
-            for (int v = 0; v < FVM_MAXV; v++) Sq[v] = 0.0;
-            PDE::source(qc, Sq);
-            const double hdt = 0.5 * dt;
-#pragma unroll
-            for (int v = 0; v < FVM_MAXV; v++)
-                if (v < m) dl[v] = -hr * sum[v] + hdt * Sq[v];
-        } else {
-#pragma unroll
-            for (int v = 0; v < FVM_MAXV; v++)
-                if (v < m) dl[v] = -hr * sum[v];
-        }
+        for (int e = 0; e < DIM; e++) nb.qm[e] = nb.qp[e] = tst[e] * V;
+        fv_muscl_predict_volume<DIM, PDE>(q, nb, del + ((long)pp * dvol + dc) * m, m, hr, dt);
     }
 }
 
@@ -179,74 +256,35 @@ __device__ __forceinline__ double fv_muscl_correct(const double* img, const doub
         for (int a = 0; a < DIM; a++) { tc += (co[a] + 2) * tst[a]; dc += (co[a] + 1) * dst[a]; }
         const double* q = img + ((long)pp * tvol + tc) * V;
         const double* dl = del + ((long)pp * dvol + dc) * m;
-        double qc[FVM_MAXV], dC[FVM_MAXV], acc[FVM_MAXV];
+        FvMusclNbr nb;
 #pragma unroll
-        for (int v = 0; v < FVM_MAXV; v++) { qc[v] = v < m ? q[v] : 0.0; dC[v] = v < m ? dl[v] : 0.0; acc[v] = 0.0; }
-        [[maybe_unused]] double qh[FVM_MAXV];                     // the half-step state Q_c + delta_c, where the volume's own terms are taken
-        if constexpr (pde_has_ncp<PDE>::value || pde_has_source<PDE>::value) {
-#pragma unroll
-            for (int v = 0; v < FVM_MAXV; v++) qh[v] = qc[v] + dC[v];
-        }
-        static_for_muscl<0, DIM>([&](auto dd) {
-            constexpr int d = decltype(dd)::value;
+        for (int d = 0; d < DIM; d++) {
             const int qs = tst[d] * V, ds = dst[d] * m;
-            double sC[FVM_MAXV], sN[FVM_MAXV], wCp[FVM_MAXV], wCm[FVM_MAXV], wN[FVM_MAXV], Fp[FVM_MAXV], Fm[FVM_MAXV];
-            fv_muscl_slope(q, qs, m, sC);
-#pragma unroll
-            for (int v = 0; v < FVM_MAXV; v++) { wCp[v] = (qc[v] + 0.5 * sC[v]) + dC[v]; wCm[v] = (qc[v] - 0.5 * sC[v]) + dC[v]; }
-            fv_muscl_slope(q + qs, qs, m, sN);                    // the plus-side neighbour's minus state
-#pragma unroll
-            for (int v = 0; v < FVM_MAXV; v++) wN[v] = v < m ? (q[qs + v] - 0.5 * sN[v]) + dl[ds + v] : 0.0;
-            fv_muscl_face<PDE, d>(wCp, wN, m, Fp);
-            [[maybe_unused]] double Dp[FVM_MAXV], Dm[FVM_MAXV];
-            if constexpr (pde_has_ncp<PDE>::value) fv_muscl_jump<PDE, d>(wCp, wN, m, Dp);
-            fv_muscl_slope(q - qs, qs, m, sN);                    // the minus-side neighbour's plus state
-#pragma unroll
-            for (int v = 0; v < FVM_MAXV; v++) wN[v] = v < m ? (q[v - qs] + 0.5 * sN[v]) + dl[v - ds] : 0.0;
-            fv_muscl_face<PDE, d>(wN, wCm, m, Fm);
-#pragma unroll
-            for (int v = 0; v < FVM_MAXV; v++) acc[v] = d == 0 ? Fp[v] - Fm[v] : acc[v] + (Fp[v] - Fm[v]);
-            if constexpr (pde_has_ncp<PDE>::value) {              // + (D_{c+1/2} + D_{c-1/2}) / 2 + B_d(Q_c + delta_c) s_d(c)
-                double Bs[FVM_MAXV];
-                fv_muscl_jump<PDE, d>(wN, wCm, m, Dm);
-#pragma unroll
-                for (int v = 0; v < FVM_MAXV; v++) Bs[v] = 0.0;
-                PDE::ncp(qh, sC, d, Bs);
+            nb.qmm[d] = nb.qm[d] = nb.qp[d] = nb.qpp[d] = qs;
+            nb.dm[d] = nb.dp[d] = ds;
+        }
+        fv_muscl_correct_volume<DIM, PDE>(q, dl, nb, m, r, dt, [&](auto updated) {
+            if (out) {                                            // halo-less QOut [patch][P^DIM][V]: auxiliary variables copied
+                double* o = out + (patch * ncell + id) * V;
 #pragma unroll
                 for (int v = 0; v < FVM_MAXV; v++)
-                    if (v < m) acc[v] += (0.5 * Dp[v] + 0.5 * Dm[v]) + Bs[v];
+                    if (v < m) o[v] = updated(v);
+                for (int v = m; v < V; v++) o[v] = q[v];
+                if constexpr (LAM) {
+                    double qn[FVM_MAXV];
+#pragma unroll
+                    for (int v = 0; v < FVM_MAXV; v++) qn[v] = v < m ? updated(v) : (v < V ? q[v] : 0.0);
+#pragma unroll
+                    for (int d = 0; d < DIM; d++) lmax = nan_max(lmax, PDE::maxeig(qn, d));
+                }
+            } else {
+                const long c = DIM == 3 ? ((long)(co[0] + H) * S + (co[1] + H)) * S + (co[2] + H) : (long)(co[0] + H) * S + (co[1] + H);
+                double* o = Q + (patch * svol + c) * V;
+#pragma unroll
+                for (int v = 0; v < FVM_MAXV; v++)
+                    if (v < m) o[v] = updated(v);
             }
         });
-        [[maybe_unused]] double Sq[FVM_MAXV];                     // S(Q_c + delta_c): the source at the half-step state
-        if constexpr (pde_has_source<PDE>::value) {
-#pragma unroll
-            for (int v = 0; v < FVM_MAXV; v++) Sq[v] = 0.0;
-            PDE::source(qh, Sq);
-        }
-        auto updated = [&](int v) -> double {                     // the new value of evolved variable v
-            if constexpr (pde_has_source<PDE>::value) return (qc[v] - r * acc[v]) + dt * Sq[v];
-            else return qc[v] - r * acc[v];
-        };
-        if (out) {                                                // halo-less QOut [patch][P^DIM][V]: auxiliary variables copied
-            double* o = out + (patch * ncell + id) * V;
-#pragma unroll
-            for (int v = 0; v < FVM_MAXV; v++)
-                if (v < m) o[v] = updated(v);
-            for (int v = m; v < V; v++) o[v] = q[v];
-            if constexpr (LAM) {
-                double qn[FVM_MAXV];
-#pragma unroll
-                for (int v = 0; v < FVM_MAXV; v++) qn[v] = v < m ? updated(v) : (v < V ? q[v] : 0.0);
-#pragma unroll
-                for (int d = 0; d < DIM; d++) lmax = nan_max(lmax, PDE::maxeig(qn, d));
-            }
-        } else {
-            const long c = DIM == 3 ? ((long)(co[0] + H) * S + (co[1] + H)) * S + (co[2] + H) : (long)(co[0] + H) * S + (co[1] + H);
-            double* o = Q + (patch * svol + c) * V;
-#pragma unroll
-            for (int v = 0; v < FVM_MAXV; v++)
-                if (v < m) o[v] = updated(v);
-        }
     }
     return lmax;
 }
@@ -321,6 +359,146 @@ int fv_muscl_run(int P, int H, int m, int V, long n_patches, double* Q, double d
         if (pl.nt == 512) return go(fv_muscl_kernel<DIM, PDE, 512>, 512);
     }
     return go(fv_muscl_kernel<DIM, PDE, 256>, 256);
+}
+
+// ---- the PLANE-STREAMING form (3-D; a plan of exa_fv_plan_create_streamed): for patches whose whole window does not fit a compute unit's LDS.  One
+// workgroup per patch walks the planes of axis 0 once and keeps a ring of `ring` window planes [T][T][V] and three predictor planes [D][D][m]:
+//   step s = 0 .. T - 1:   stage window plane s                     (H = 2: one contiguous block of the patch, 16-byte loads; else row by row)
+//                          barrier
+//                          predictor plane s - 2                    (box plane d reads window planes d .. d + 2; the plus-shape rule as ever)
+//                          barrier
+//                          interior plane s - 4: compute and store  (interior plane i reads window planes i .. i + 4, predictor planes i .. i + 2)
+//                          ring == 5: barrier                       (the next stage overwrites window plane s - 4, which this step still read)
+// With a sixth slot the next stage overwrites plane s - 5, which nobody reads any more: two barriers per plane, and the loads of plane s + 1 are on
+// their way while the slower lanes still finish plane s - 4.  The per-volume arithmetic is fv_muscl_predict_volume / fv_muscl_correct_volume -- the
+// functions of the resident kernel on the same operands, so the results are bit-identical wherever both serve a shape; only the axis-0 neighbours
+// stand at the distances of their ring slots.
+// IN PLACE IS SAFE BECAUSE every plane of the patch is read from HBM before its interior is written: window plane w is staged in step w, the interior
+// of that plane (interior plane w - 2) is stored in step w + 2, and from its staging on the plane is read from the ring only.  Nothing may read Q
+// behind the walk.
+template <class PDE, int NT>
+__global__ void __launch_bounds__(NT)
+fv_muscl_stream_kernel(double* __restrict__ Q, double* __restrict__ out, const long* __restrict__ slot, int P, int H, int m, int V, double r, int ring,
+                       double dt) {
+    extern __shared__ __attribute__((aligned(16))) double fvm_lds[];
+    const long patch = (long)blockIdx.x;
+    if (slot && slot[patch] < 0) return;                          // the whole workgroup, before any load and any barrier
+    const int S = P + 2 * H, T = P + 4, D = P + 2, off = H - 2;
+    const int wpl = T * T * V, ppl = D * D * m;                   // doubles of a window plane / a predictor plane
+    const long svol = (long)S * S * S;
+    double* win = fvm_lds;                                        // [ring][T][T][V]
+    double* pre = fvm_lds + (long)ring * wpl;                     // [3][D][D][m]
+    const double* src = Q + patch * svol * V;
+    const int tid = (int)threadIdx.x;
+    const double hr = 0.5 * r;
+    for (int s = 0; s < T; s++) {
+        // ---- stage window plane s
+        double* dst = win + (s % ring) * wpl;
+        if (off == 0) {                                           // the plane is one contiguous block of the patch
+            const double* sp = src + (long)s * wpl;
+            const unsigned long long sa = reinterpret_cast<unsigned long long>(sp), da = reinterpret_cast<unsigned long long>(dst);
+            if (((sa ^ da) & 15) == 0) {                          // both reach a 16-byte boundary after the same `head` doubles
+                const int head = (int)((sa >> 3) & 1), nv = (wpl - head) / 2;
+                const fvm_v2d* s2 = reinterpret_cast<const fvm_v2d*>(sp + head);
+                fvm_v2d* d2 = reinterpret_cast<fvm_v2d*>(dst + head);
+                for (int i = tid; i < nv; i += NT) d2[i] = s2[i];
+                if (tid == 0) {
+                    if (head) dst[0] = sp[0];
+                    if ((wpl - head) & 1) dst[wpl - 1] = sp[wpl - 1];
+                }
+            } else {
+                for (int i = tid; i < wpl; i += NT) dst[i] = sp[i];
+            }
+        } else {                                                  // H > 2: rows of T V contiguous doubles
+            const int row = T * V;
+            for (int i = tid; i < wpl; i += NT) {
+                const int rw = i / row, x = i - rw * row;
+                dst[i] = src[(((long)(s + off) * S + (rw + off)) * S + off) * V + x];
+            }
+        }
+        __syncthreads();
+
+        // ---- predictor plane d0 = s - 2 (box coordinates): window plane d0 + 1, neighbours in planes d0 and d0 + 2
+        if (s >= 2) {
+            const int d0 = s - 2, o0 = (d0 < 1 || d0 > P) ? 1 : 0;
+            const int w0 = d0 % ring, w1 = (d0 + 1) % ring, w2 = (d0 + 2) % ring;
+            const double* wc = win + w1 * wpl;
+            double* pc = pre + (d0 % 3) * ppl;
+            FvMusclNbr nb;
+            nb.qm[0] = (w1 - w0) * wpl; nb.qp[0] = (w2 - w1) * wpl;
+            nb.qm[1] = nb.qp[1] = T * V;
+            nb.qm[2] = nb.qp[2] = V;
+            for (int i = tid; i < D * D; i += NT) {
+                const int y = i / D, x = i - y * D;
+                if (o0 + ((y < 1 || y > P) ? 1 : 0) + ((x < 1 || x > P) ? 1 : 0) > 1) continue;
+                fv_muscl_predict_volume<3, PDE>(wc + ((y + 1) * T + (x + 1)) * V, nb, pc + (y * D + x) * m, m, hr, dt);
+            }
+        }
+        __syncthreads();
+
+        // ---- interior plane i0 = s - 4: window plane i0 + 2 with planes i0 .. i0 + 4 around it, predictor plane i0 + 1 between i0 and i0 + 2
+        if (s >= 4) {
+            const int i0 = s - 4;
+            int w[5], p[3];
+#pragma unroll
+            for (int k = 0; k < 5; k++) w[k] = (i0 + k) % ring;
+#pragma unroll
+            for (int k = 0; k < 3; k++) p[k] = (i0 + k) % 3;
+            const double* wc = win + w[2] * wpl;
+            const double* pc = pre + p[1] * ppl;
+            FvMusclNbr nb;
+            nb.qmm[0] = (w[1] - w[0]) * wpl; nb.qm[0] = (w[2] - w[1]) * wpl; nb.qp[0] = (w[3] - w[2]) * wpl; nb.qpp[0] = (w[4] - w[3]) * wpl;
+            nb.dm[0] = (p[1] - p[0]) * ppl; nb.dp[0] = (p[2] - p[1]) * ppl;
+            nb.qmm[1] = nb.qm[1] = nb.qp[1] = nb.qpp[1] = T * V;
+            nb.qmm[2] = nb.qm[2] = nb.qp[2] = nb.qpp[2] = V;
+            nb.dm[1] = nb.dp[1] = D * m;
+            nb.dm[2] = nb.dp[2] = m;
+            for (int i = tid; i < P * P; i += NT) {
+                const int y = i / P, x = i - y * P;
+                const double* q = wc + ((y + 2) * T + (x + 2)) * V;
+                fv_muscl_correct_volume<3, PDE>(q, pc + ((y + 1) * D + (x + 1)) * m, nb, m, r, dt, [&](auto updated) {
+                    if (out) {                                    // halo-less QOut [patch][P^3][V]: auxiliary variables copied
+                        double* o = out + ((patch * P + i0) * (long)(P * P) + i) * V;
+#pragma unroll
+                        for (int v = 0; v < FVM_MAXV; v++)
+                            if (v < m) o[v] = updated(v);
+                        for (int v = m; v < V; v++) o[v] = q[v];
+                    } else {                                      // in place: this plane of Q was staged two steps ago (see above)
+                        double* o = Q + (patch * svol + ((long)(i0 + H) * S + (y + H)) * S + (x + H)) * V;
+#pragma unroll
+                        for (int v = 0; v < FVM_MAXV; v++)
+                            if (v < m) o[v] = updated(v);
+                    }
+                });
+            }
+        }
+        if (ring == 5) __syncthreads();                           // (the next stage reuses the slot of window plane s - 4)
+    }
+}
+
+// launch of the streamed form for one PDE; the plan is fv_muscl_stream_plan's, which exa_fv_plan_create_streamed has checked
+template <class PDE>
+int fv_muscl_stream_run(int P, int H, int m, int V, long n_patches, double* Q, double dt, double h, const long* slot, hipStream_t s, double* out) {
+    FvMusclPlan pl;
+    if (P < 1 || P > 1024 || !fv_muscl_stream_plan(P, m, V, &pl)) {
+        set_error("MUSCL-Hancock (streamed): five window planes and three predictor planes need %zu B of LDS, %zu B are available",
+                  P >= 1 && P <= 1024 ? pl.lds : (size_t)-1, FV_MUSCL_LDS_AVAILABLE);
+        return -1;
+    }
+    if (H < 2) { set_error("MUSCL-Hancock reads two halo layers"); return -1; }
+    if (m > FVM_MAXV) { set_error("n_real = %d exceeds %d", m, FVM_MAXV); return -1; }
+    if (n_patches <= 0) return 0;
+    if (n_patches > 0x7fffffffL) { set_error("MUSCL-Hancock: %ld patches are more than one launch covers", n_patches); return -1; }
+    const double r = dt / h;
+    auto kern = fv_muscl_stream_kernel<PDE, 256>;
+    if (pl.lds > 64 * 1024) {
+        hipError_t ea = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)pl.lds);
+        if (ea != hipSuccess) { set_error("hipFuncSetAttribute(fv muscl stream, %zu B LDS): %s", pl.lds, hipGetErrorString(ea)); return -2; }
+    }
+    hipLaunchKernelGGL(kern, dim3((unsigned)n_patches), dim3(pl.nt), pl.lds, s, Q, out, slot, P, H, m, V, r, pl.ring, dt);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) { set_error("fv_muscl stream launch: %s", hipGetErrorString(e)); return -2; }
+    return 0;
 }
 
 // ---- the GRID step (exa_fv_grid_step_muscl_device): the patches are the cells of a Cartesian grid g[0] x g[1] (x g[2]), patch index row-major,

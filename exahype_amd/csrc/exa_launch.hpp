@@ -120,6 +120,7 @@ constexpr size_t FV_MUSCL_LDS_AVAILABLE = 160 * 1024;
 struct FvMusclPlan {
     int ppb, nt;
     size_t lds;
+    int ring = 0;          // window planes in LDS at a time (fv_muscl_stream_plan; 0: the whole window, fv_muscl_plan)
 };
 inline bool fv_muscl_plan(int dim, int P, int n_real, int V, FvMusclPlan* pl) {
     const size_t T = (size_t)P + 4, D = (size_t)P + 2;
@@ -136,11 +137,33 @@ inline bool fv_muscl_plan(int dim, int P, int n_real, int V, FvMusclPlan* pl) {
     }
     return true;
 }
+// The plan of the PLANE-STREAMING form of the 3-D update (fv_muscl_stream_kernel): one workgroup per patch walks the planes of axis 0 and keeps
+// `ring` window planes (P + 4)^2 x V and three predictor planes (P + 2)^2 x n_real in LDS.  Five window planes are what an interior plane reads; a
+// sixth, where it fits, takes the next plane while the oldest one is still read and saves one of the three barriers per plane.  256 threads: a plane
+// has at most 19^2 interior and 21^2 predictor tasks, and the arithmetic needs more registers than a lane of a 512-thread workgroup has.
+// -> false: five + three planes do not fit (pl->lds = the bytes they need)
+inline bool fv_muscl_stream_plan(int P, int n_real, int V, FvMusclPlan* pl) {
+    const size_t T = (size_t)P + 4, D = (size_t)P + 2;
+    const size_t wpl = T * T * (size_t)V, ppl = D * D * (size_t)n_real;
+    const size_t five = (5 * wpl + 3 * ppl) * sizeof(double), six = five + wpl * sizeof(double);
+    pl->ppb = 1;
+    pl->nt = 256;
+    pl->ring = 5;
+    pl->lds = five;
+    if (five > FV_MUSCL_LDS_AVAILABLE) return false;
+    if (six <= FV_MUSCL_LDS_AVAILABLE) { pl->ring = 6; pl->lds = six; }
+    return true;
+}
 // out != nullptr: out of place (QOut halo-less); slot: as fv_launch
 int fv_muscl_launch(int dim, int P, int H, int n_real, int n_aux, long n_patches, int pde, double* Q, double dt, double h, const long* slot,
                     hipStream_t s, double* out);
 int user_fv_muscl_launch(int pde, int dim, int P, int H, int n_real, int n_aux, long n_patches, double* Q, double dt, double h, const long* slot,
                          hipStream_t s, double* out);
+// the same update by the plane-streaming kernel (3-D; a plan created with exa_fv_plan_create_streamed that is_streamed): same arguments, same results
+int fv_muscl_stream_launch(int P, int H, int n_real, int n_aux, long n_patches, int pde, double* Q, double dt, double h, const long* slot, hipStream_t s,
+                           double* out);
+int user_fv_muscl_stream_launch(int pde, int P, int H, int n_real, int n_aux, long n_patches, double* Q, double dt, double h, const long* slot,
+                                hipStream_t s, double* out);
 // the GRID step of this mode (exa_fv_grid_step_muscl_device; fv_muscl_grid_kernel): Q and out halo-less [patch][P^dim][V], the patches the cells of
 // the grid g (row-major); bstate == null: every domain face periodic, else face (axis, side) is of kind bkind[axis * 2 + side] (FV_FACE_*) with its V
 // doubles of data in bstate[(axis * 2 + side) * V ..]; lam (optional): receives the largest eigenvalue of the NEW states (zeroed by the launcher)

@@ -22,6 +22,18 @@ extern "C" int exa_user_fv_muscl_launch(int dim, int P, int H, int n_real, int n
     return -1;
 }
 
+// the plane-streaming form of the 3-D update (a plan of exa_fv_plan_create_streamed that is_streamed).  A side library built before this entry
+// existed lacks it: exa_register_pde still takes such a library, exa_fv_plan_create_streamed refuses a streamed plan of its term set until it is rebuilt
+extern "C" int exa_user_fv_muscl_stream_launch(int P, int H, int n_real, int n_aux, long n_patches, double* Q, double dt, double h, const long* slot,
+                                               void* stream, double* out) {
+    using namespace exa;
+    const int V = n_real + n_aux;
+    if (n_real > FVM_MAXV || n_real < UserPDE::NV) { set_error("user PDE evolves %d variables; n_real = %d", UserPDE::NV, n_real); return -1; }
+    if constexpr (UserPDE::MAXDIM >= 3) return fv_muscl_stream_run<UserPDE>(P, H, n_real, V, n_patches, Q, dt, h, slot, (hipStream_t)stream, out);
+    set_error("user PDE: no streamed MUSCL-Hancock kernel (the term set is 2-D)");
+    return -1;
+}
+
 // the grid step on halo-less arrays (exa_fv_grid_step_muscl_device); grid: exa::FvMusclGrid.  A side library built before this entry existed
 // lacks it: exa_register_pde still takes such a library, the grid step refuses its term set until it is rebuilt
 extern "C" int exa_user_fv_muscl_grid_launch(int dim, int P, int n_real, int n_aux, long n_patches, const double* Q, double* out, double dt, double h,

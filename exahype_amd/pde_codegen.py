@@ -154,7 +154,8 @@ class SympyPDE:
         muscl_hancock=True (keyword only): the term set asks for the second-order MUSCL-Hancock patch update (FVRusanovKernel / FVPatchGrid /
         HIPPrinter with mode FV_MUSCL_HANCOCK).  The generated struct then carries HAS_MUSCL_HANCOCK and the side library one more unit
         (csrc/fv_muscl_user.hip: exa_user_fv_muscl_launch and, for the one-launch grid step FVPatchGrid(fused=FUSED_EDGES),
-        exa_user_fv_muscl_grid_launch; a cached library from before that entry still registers, the grid step asks for a rebuild).  The scheme -- slopes, half-step predictor, Rusanov flux of the predicted face
+        exa_user_fv_muscl_grid_launch; a cached library from before that entry still registers, the grid step asks for a rebuild; and, for
+        3-D patches walked plane by plane (FVRusanovKernel(stream_planes=...)), exa_user_fv_muscl_stream_launch, resolved the same way).  The scheme -- slopes, half-step predictor, Rusanov flux of the predicted face
         states -- is written for conservative terms of the state alone: terms that depend on position / time, an ncp or a source raise
         ValueError.  Without the keyword the generated source, the cache key and the build are what they were, and a plan in that mode on such a
         term set is refused.
@@ -687,8 +688,9 @@ struct UserPDE {
         if self.conservative_interface:                                # (... and so is the unit of the conservative interface)
             for f in ("lim_conserve_user.hip", "exa_lim_conserve.hpp", "exa_lim_detect.hpp"):
                 h.update(open(os.path.join(CSRC, f), "rb").read())
-        if self.muscl_hancock:                                         # (... and the unit of the second-order patch update)
-            for f in ("fv_muscl_user.hip", "exa_fv_muscl.hpp"):
+        if self.muscl_hancock:                                         # (... and the unit of the second-order patch update: a library cached
+            for f in ("fv_muscl_user.hip", "exa_fv_muscl.hpp"):        # before an entry was added to it -- exa_user_fv_muscl_grid_launch,
+                                                                       # exa_user_fv_muscl_stream_launch -- has another key and is rebuilt)
                 h.update(open(os.path.join(CSRC, f), "rb").read())
         h.update(open(os.path.join(os.path.dirname(os.path.abspath(__file__)), "build.py"), "rb").read())      # (compiler flags)
         h.update(repr(self.dg_flags).encode())

@@ -143,10 +143,11 @@ def _same_statements(a: KernelBuilder, b: KernelBuilder):
 
 class HIPPrinter(CodePrinter):
     def __init__(self: HIPPrinter, kernel: KernelBuilder, function_name: str = "time_step", scheme: str = None,
-                 pde: str = None, grid=None, n_picard: int = -1, device: int = 0):
+                 pde: str = None, grid=None, n_picard: int = -1, device: int = 0, stream_planes: int = 0):
         super().__init__(kernel, function_name=function_name)
         k = kernel
         self.device = device
+        self.stream_planes = int(stream_planes)     # scheme='fv-muscl-hancock': FV_STREAM_* (FVRusanovKernel), passed on to the plan
         self._impl = None
         self.lowering = None
         self.cell_data = False
@@ -304,10 +305,16 @@ class HIPPrinter(CodePrinter):
             if mode == 2 and getattr(self.user_pde, "muscl_terms", False):
                 L += ["//              the term set's source enters by the midpoint rule in time, its non-conservative product in the predictor, as the",
                       "//              jump term of the predicted face states and at the half-step state (SympyPDE(muscl_hancock=True, muscl_terms=True))"]
-            L += [
+            if self.stream_planes:
+                L += ["//              stream_planes = %d: 3-D patches beyond the resident plan are walked plane by plane (fv_muscl_stream_kernel)" % self.stream_planes,
+                      "// C-ABI      : exa_fv_plan_create_streamed(dev, %d, %d, %d, %d, %d, %d, %d, %d, %d, &plan); exa_fv_time_step_device(plan, %s, %s, h, stream)"
+                      % (mode, k.dim, k.patch_size, k.halo_size, k.n_real, k.n_aux, k.n_patches, self.pde, self.stream_planes,
+                         k.items[0] if k.items else "Q", k.inputs[0] if k.inputs else "dt")]
+            L += [] if self.stream_planes else [
                   "// C-ABI      : exa_fv_plan_create(dev, %d, %d, %d, %d, %d, %d, %d, %d, &plan); exa_fv_time_step_device(plan, %s, %s, h, stream)"
                   % (mode, k.dim, k.patch_size, k.halo_size, k.n_real, k.n_aux, k.n_patches, self.pde, k.items[0] if k.items else "Q",
-                     k.inputs[0] if k.inputs else "dt"),
+                     k.inputs[0] if k.inputs else "dt")]
+            L += [
                   "// arrays     : %s[%d][%s][%d] fp64, AoS (reference layout), interior updated in place"
                   % (k.items[0] if k.items else "Q", k.n_patches, "][".join([str(S)] * k.dim), V)]
         L.append("// statements :")
@@ -353,7 +360,7 @@ class HIPPrinter(CodePrinter):
             else:
                 mode = {"fv-rusanov-faithful": solvers.FV_FAITHFUL, "fv-rusanov": solvers.FV_RUSANOV, "fv-muscl-hancock": solvers.FV_MUSCL_HANCOCK}[self.scheme]
                 self._impl = solvers.FVRusanovKernel(k.dim, k.patch_size, k.halo_size, k.n_real, k.n_aux, k.n_patches,
-                                                     pde=self.pde, mode=mode, device=self.device)
+                                                     pde=self.pde, mode=mode, device=self.device, stream_planes=self.stream_planes)
         return self._impl
 
     def run(self, Q, *consts, h=1.0, dx=None, steps=1):

@@ -14,7 +14,7 @@ import os
 import numpy as np
 
 from . import _lib
-from ._lib import (FV_FAITHFUL, FV_MUSCL_HANCOCK, FV_RUSANOV, PDE_ADVECTION, PDE_EULER, PDE_EULER_REF2D, PDE_FLAG_MUSCL_HANCOCK, PDE_FLAG_MUSCL_TERMS, PDE_FLAG_NCP,
+from ._lib import (FV_FAITHFUL, FV_MUSCL_HANCOCK, FV_RUSANOV, FV_STREAM_ALWAYS, FV_STREAM_IF_NEEDED, FV_STREAM_NEVER, PDE_ADVECTION, PDE_EULER, PDE_EULER_REF2D, PDE_FLAG_MUSCL_HANCOCK, PDE_FLAG_MUSCL_TERMS, PDE_FLAG_NCP,
                    PDE_FLAG_XT, check, darr, larr)
 from .boundary import Dirichlet, Outflow, Wall, coefficients as _bc_coefficients, fv_faces as _fv_faces, validate_boundary
 
@@ -41,18 +41,32 @@ class FVRusanovKernel:
     mode needs halo_size >= 2 and reads the EDGE entries of the two halo layers next to the interior (layer 1 along two axes) beside the
     face entries; it serves PDE_EULER, PDE_ADVECTION and term sets generated with SympyPDE(..., muscl_hancock=True) (conservative terms of the
     state alone; with muscl_terms=True also a source and / or a non-conservative product of the state alone), ignores `centres` / `t`,
-    and a patch whose LDS plan does not fit a compute unit is refused when the kernel object is created."""
+    and a patch whose LDS plan does not fit a compute unit is refused when the kernel object is created.
+
+    stream_planes (FV_MUSCL_HANCOCK, 3-D): FV_STREAM_NEVER (default) -- the whole window of a patch resident in LDS, 3-D patch_size <= 8 with five
+    variables; FV_STREAM_IF_NEEDED -- larger patches (up to 19 with five variables) are walked plane by plane (fv_muscl_stream_kernel), with
+    bit-identical per-volume arithmetic; FV_STREAM_ALWAYS -- plane by plane wherever that plan exists (tests, measurements).  `.streamed` says which
+    form serves the object."""
 
     def __init__(self, dim, patch_size, halo_size, n_real, n_aux, n_patches=1, pde=PDE_EULER_REF2D,
-                 mode=FV_FAITHFUL, device=0):
+                 mode=FV_FAITHFUL, device=0, stream_planes=FV_STREAM_NEVER):
         self.lib = _lib.load()
         self.shape = (n_patches,) + (patch_size + 2 * halo_size,) * dim + (n_real + n_aux,)
         self.device = device
         h = C.c_void_p()
-        check(self.lib.exa_fv_plan_create(device, mode, dim, patch_size, halo_size, n_real, n_aux, n_patches, pde,
-                                          C.byref(h)))
+        if stream_planes == FV_STREAM_NEVER:
+            check(self.lib.exa_fv_plan_create(device, mode, dim, patch_size, halo_size, n_real, n_aux, n_patches, pde,
+                                              C.byref(h)))
+        else:
+            check(self.lib.exa_fv_plan_create_streamed(device, mode, dim, patch_size, halo_size, n_real, n_aux, n_patches, pde, int(stream_planes),
+                                                       C.byref(h)))
         self._plan = h
         self.count = self.lib.exa_fv_q_count(h)
+
+    @property
+    def streamed(self):
+        """True if the plane-streaming kernel serves this object (exa_fv_plan_is_streamed)."""
+        return bool(self.lib.exa_fv_plan_is_streamed(self._plan))
 
     def time_step(self, Q, dt, h=1.0, slot=None, t=0.0, centres=None):
         """In place.  numpy array -> staged through HBM by the library; CUDA tensor -> no copies.
@@ -904,7 +918,7 @@ class FVPatchGrid:
     it has its twin's eigenvalue and takes no part in the CFL scan, the prescribed states do."""
 
     def __init__(self, dim, grid, patch_size, halo_size=1, n_real=5, n_aux=0, pde=PDE_EULER, mode=FV_RUSANOV,
-                 length=1.0, device=0, boundary=None, origin=None, time=0.0, fused=True):
+                 length=1.0, device=0, boundary=None, origin=None, time=0.0, fused=True, stream_planes=FV_STREAM_NEVER):
         """origin, time: physical coordinates of the grid's low corner and the start time -- reach term sets whose terms depend on position /
         time (the patch centres follow from them); step() / run() advance the time.
 
@@ -914,7 +928,10 @@ class FVPatchGrid:
         mode=FV_MUSCL_HANCOCK (second order) runs with halo_size >= 2 and fused=FUSED_EDGES or fused=False: its stencil reads the edge entries of
         the halo, which belong to diagonal patches -- the FUSED_EDGES step gathers them in the patch kernel, the halo fills of the two-pass form
         supply them, the one-launch step behind fused=True takes face neighbours only and refuses.  halo_size only shapes `with_halo()` under
-        FUSED_EDGES: the arrays of the step have no halo."""
+        FUSED_EDGES: the arrays of the step have no halo.
+
+        stream_planes (FVRusanovKernel): with fused=False, FV_STREAM_IF_NEEDED serves 3-D patches of mode=FV_MUSCL_HANCOCK beyond patch_size 8
+        plane by plane.  The one-launch step is not built for that form: fused=FUSED_EDGES with a shape that would stream raises ValueError."""
         edges = isinstance(fused, str) and fused == FUSED_EDGES
         if isinstance(fused, str) and not edges:
             raise ValueError("FVPatchGrid(fused=%r): True, False or FUSED_EDGES (%r)" % (fused, FUSED_EDGES))
@@ -936,7 +953,11 @@ class FVPatchGrid:
         self.n_real, self.n_aux, self.pde = n_real, n_aux, pde
         self.h = length / (self.grid[0] * patch_size)                  # volume size
         n_patches = int(np.prod(self.grid))
-        self.kernel = FVRusanovKernel(dim, patch_size, halo_size, n_real, n_aux, n_patches, pde, mode, device)
+        self.kernel = FVRusanovKernel(dim, patch_size, halo_size, n_real, n_aux, n_patches, pde, mode, device, stream_planes=stream_planes)
+        if edges and self.kernel.streamed:
+            raise ValueError("FVPatchGrid(fused=FUSED_EDGES, stream_planes=%r): patches of %d^%d volumes with %d + %d variables are served plane by "
+                             "plane, and the one-launch step is not built for that form -- use fused=False (halo fills, then the in-place update)"
+                             % (stream_planes, patch_size, dim, n_real, n_aux))
         self.lib = self.kernel.lib
         self.dev = torch.device("cuda", device)
         self.fused = bool(fused)                                      # the states live halo-less in `.U`
@@ -1142,7 +1163,7 @@ class SubcellLimiter:
 
     DEFAULT_FRACTION = 0.1          # default capacity: this share of the block's cells (at least 16)
 
-    def __init__(self, solver, capacity=None, fv_mode=FV_RUSANOV):
+    def __init__(self, solver, capacity=None, fv_mode=FV_RUSANOV, stream_planes=FV_STREAM_NEVER):
         """fv_mode: the patch update of the troubled cells.  FV_RUSANOV (default): first order, patches with halo 1.  FV_MUSCL_HANCOCK: the
         second-order update (FVRusanovKernel) on patches with halo 2 -- face halos two layers deep and the edge entries from the diagonal
         cells (exa_lim_project_patches_halo2); the domain faces' conditions enter the projection as mirror / state faces (Outflow: a mirror
@@ -1151,6 +1172,9 @@ class SubcellLimiter:
         muscl_terms=True: the limiter's restatement of the update knows neither a source nor an ncp) and patches whose
         LDS plan fits a compute unit (five variables: every 2-D order, 3-D N <= 5); anything else raises ValueError here.  Not together
         with conservative=True.
+
+        stream_planes (with fv_mode=FV_MUSCL_HANCOCK; FVRusanovKernel): FV_STREAM_IF_NEEDED serves the 3-D orders beyond that -- N = 6, 7, 8, patches
+        of 11, 13 and 15 volumes per axis -- by the plane-streaming kernel; the default FV_STREAM_NEVER refuses them as before.
 
         capacity: upper bound of the number of troubled cells per step; the FV patch array [capacity][(N_s+2)^dim][n_vars]
         is allocated once (196 KB per patch at p = 7) and the glue kernels launch `capacity` workgroups per step, so the
@@ -1165,7 +1189,10 @@ class SubcellLimiter:
         self.Ns = 2 * solver.N - 1
         if fv_mode not in (FV_RUSANOV, FV_MUSCL_HANCOCK):
             raise ValueError("SubcellLimiter: fv_mode must be FV_RUSANOV or FV_MUSCL_HANCOCK, got %r" % (fv_mode,))
+        if stream_planes != FV_STREAM_NEVER and fv_mode != FV_MUSCL_HANCOCK:
+            raise ValueError("SubcellLimiter: stream_planes is a choice of fv_mode=FV_MUSCL_HANCOCK")
         self.fv_mode = fv_mode
+        self.stream_planes = stream_planes
         self.fv_halo = 2 if fv_mode == FV_MUSCL_HANCOCK else 1
         if fv_mode == FV_MUSCL_HANCOCK:
             self._muscl_refusals()
@@ -1240,12 +1267,17 @@ class SubcellLimiter:
         patch exceeds a compute unit: its message names both byte counts) is a ValueError that carries that message."""
         s = self.s
         try:
-            return FVRusanovKernel(s.dim, self.Ns, 2, s.nv, 0, self.capacity, pde=s.pde, mode=FV_MUSCL_HANCOCK, device=s.dev.index or 0)
+            return FVRusanovKernel(s.dim, self.Ns, 2, s.nv, 0, self.capacity, pde=s.pde, mode=FV_MUSCL_HANCOCK, device=s.dev.index or 0,
+                                   stream_planes=self.stream_planes)
         except _lib.ExaHypeHipError as e:
             if "bytes of LDS" not in str(e):
                 raise
+            if self.stream_planes != FV_STREAM_NEVER:
+                raise ValueError("SubcellLimiter(fv_mode=FV_MUSCL_HANCOCK, stream_planes=%r): order N = %d in %d-D is not served -- %s: use a lower "
+                                 "order or fv_mode=FV_RUSANOV" % (self.stream_planes, s.N, s.dim, e)) from None
             raise ValueError("SubcellLimiter(fv_mode=FV_MUSCL_HANCOCK): order N = %d in %d-D is not served -- %s; larger patches need plane "
-                             "streaming (DESIGN.md 8 c), which is not built: use a lower order or fv_mode=FV_RUSANOV" % (s.N, s.dim, e)) from None
+                             "streaming (stream_planes=FV_STREAM_IF_NEEDED; DESIGN.md 4.3d): pass it, use a lower order or fv_mode=FV_RUSANOV"
+                             % (s.N, s.dim, e)) from None
 
     def operators(self):
         N, Ns = self.s.N, self.Ns

@@ -68,7 +68,8 @@ extern "C" {
  *     are not served in this mode.  EXA_PDE_EULER_REF2D (F[4] never written) is refused.
  *   - exa_fv_plan_create refuses (EXA_ERR_INVALID) a shape whose LDS plan -- 8 ((patch_size + 4)^dim (n_real + n_aux) + (patch_size + 2)^dim
  *     n_real) bytes for one patch -- exceeds the 160 KiB of a compute unit; the message names both figures.  Served: 2-D patch_size <= 32
- *     with 5 variables, <= 20 with 10; 3-D patch_size <= 8 with up to 6.  Larger 3-D patches would need plane streaming: not built.
+ *     with 5 variables, <= 20 with 10; 3-D patch_size <= 8 with up to 6.  Larger 3-D patches are served plane by plane, by a plan of
+ *     exa_fv_plan_create_streamed (below): up to patch_size 19 with 5 variables.
  *   - exa_fv_grid_step_device[_bc] return EXA_ERR_INVALID: the one-launch grid step takes face neighbours only, this scheme needs the edge
  *     neighbours (diagonal patches); fill the halos of the array with halo and call exa_fv_time_step_device.
  *   - exa_fv_grid_step_muscl_device IS the one-launch grid step of this mode, on halo-less arrays: its kernel gathers the window of a patch from
@@ -124,6 +125,23 @@ int exa_pde_eval_device_at(int pde, int normal, long n, int stride, const double
 /* ---- Finite-Volume Rusanov patch update (test.h:3) -------------------------- */
 int exa_fv_plan_create(int device, int mode, int dim, int patch_size, int halo_size, int n_real, int n_aux,
                        long n_patches, int pde, exa_fv_plan** plan);
+/* The same with the choice of the PLANE-STREAMING form of EXA_FV_MUSCL_HANCOCK in 3-D: one workgroup per patch walks the planes of axis 0 and
+ * keeps five or six window planes (patch_size + 4)^2 (n_real + n_aux) and three predictor planes (patch_size + 2)^2 n_real in LDS instead of the
+ * whole window -- 8 (5 (P + 4)^2 V + 3 (P + 2)^2 n_real) bytes must fit the 160 KiB (5 + 0 variables: patch_size <= 19).  The per-volume
+ * arithmetic is the resident kernel's: where both serve a shape the results are bit-identical.
+ *   EXA_FV_STREAM_NEVER      what exa_fv_plan_create does
+ *   EXA_FV_STREAM_IF_NEEDED  the resident plan where it fits, the streamed one where not (3-D; in 2-D as NEVER)
+ *   EXA_FV_STREAM_ALWAYS     the streamed plan wherever it exists (tests, measurements)
+ * EXA_ERR_INVALID: a non-zero stream_planes with another mode; ALWAYS in 2-D; a shape whose streamed plan does not fit (the message names the bytes
+ * of both plans); an unknown value; a registered term set whose side library was built before exa_user_fv_muscl_stream_launch existed (rebuild it).
+ * A streamed plan is served by every exa_fv_time_step_* entry and by exa_fv_max_eigenvalue; exa_fv_grid_step_muscl_device refuses it (the
+ * one-launch gather is not built for this form: use the two-pass form on the array with halo). */
+#define EXA_FV_STREAM_NEVER 0
+#define EXA_FV_STREAM_IF_NEEDED 1
+#define EXA_FV_STREAM_ALWAYS 2
+int exa_fv_plan_create_streamed(int device, int mode, int dim, int patch_size, int halo_size, int n_real, int n_aux,
+                                long n_patches, int pde, int stream_planes, exa_fv_plan** plan);
+int exa_fv_plan_is_streamed(const exa_fv_plan* plan);   /* 0 | 1 */
 int exa_fv_plan_destroy(exa_fv_plan* plan);
 /* doubles in one Q array: n_patches * (patch_size + 2*halo_size)^dim * (n_real + n_aux) */
 long exa_fv_q_count(const exa_fv_plan* plan);
