@@ -9,7 +9,8 @@ ADER-DG: every condition prescribes the ghost trace stage B reads beyond the fac
   Wall(sign=None)    state s * q_in and flux -s * F_in; a mirror image of the domain across the face for term sets with F_d(S q) = -S F_d(q),
                      S = diag(s).  sign=None: only for the built-in Euler sets (the normal momentum, variable 1 + axis, changes sign)
   Dirichlet(state)   a prescribed state: an array [n_vars] (constant), or a callable f(x, t) -> [n, n_vars] on device tensors, x: [n, 3]; the
-                     ghost is then the time average over the step's Gauss time levels of f and of its normal flux
+                     ghost is then the time average over the step's Gauss time levels of f and of its normal flux.  A constant state is
+                     its own average; its flux is averaged over the levels too where the term set's flux sees x or t
 
 FV patch grid: every condition prescribes the volumes of the halo layers beyond the face (include/exahype_hip.h exa_fv_grid_step_device_bc;
 fv_faces() below turns the dict into the kinds and the per-face data of that call):

@@ -84,7 +84,10 @@ dg_bc_dirichlet_kernel(const double* __restrict__ states, BcState<PDE::NV> cq, d
         double qs[NV], Fs[NV];
 #pragma unroll
         for (int v = 0; v < NV; v++) { qs[v] = 0.0; Fs[v] = 0.0; }
-        const int L = states ? N : 1;
+        // a constant state: one level of weight 1 -- unless the flux sees x / t, then F(q, x_y, t_l) is averaged over the levels like a
+        // function's (the interior's flux is Gauss-averaged too) while the state stays q itself, not sum_l w_l q
+        constexpr bool XT = pde_has_xt<PDE>::value;
+        const int L = (states || XT) ? N : 1;
 #pragma unroll
         for (int l = 0; l < N; l++) {
             if (l >= L) break;
@@ -94,11 +97,11 @@ dg_bc_dirichlet_kernel(const double* __restrict__ states, BcState<PDE::NV> cq, d
                 q[v] = states ? states[((t * NF + y) * N + l) * NV + v] : cq.q[v];
                 F[v] = 0.0;                                   // (a term set may write only its first NFLUX entries)
             }
-            const double wl = states ? lv.w[l] : 1.0, tl = states ? lv.t[l] : lv.t[0];
+            const double wl = L > 1 ? lv.w[l] : 1.0, tl = lv.t[l];
             fv_flux<PDE>(q, x, tl, f.d, F);
 #pragma unroll
             for (int v = 0; v < NV; v++) {
-                qs[v] += wl * q[v];
+                qs[v] = states ? qs[v] + wl * q[v] : q[v];
                 Fs[v] += wl * F[v];
             }
             if (lam) {

@@ -438,6 +438,8 @@ class AderDgSolver:
         self._lam_bc = None               # Dirichlet functions: largest eigenvalue of the states of the last step (device)
         self._lam_bc_valid = False        # ... left there by a step (before the first one run() evaluates f itself)
         self._lam_bc_const = None         # constant Dirichlet states: host maximum, applied as a clamp in run()
+        # (a term set whose eigenvalue sees x / t: a constant state's depends on where and when, and goes the way of the functions')
+        xt = _sees_position_and_time(self.lib, self.pde)
         for (d, side), bc in sorted(self.boundary.items()):
             if self.part is not None and not self.part.domain_face(d, side):
                 continue
@@ -445,9 +447,9 @@ class AderDgSolver:
             buf = torch.zeros(nt, self.ts, dtype=torch.float64, device=self.dev)
             coeff = _bc_coefficients(bc, self.nv)
             self._bc.append((d, side, bc, None if coeff is None else darr(list(coeff)), buf))
-            if isinstance(bc, Dirichlet) and not bc.constant and self._lam_bc is None:
+            if isinstance(bc, Dirichlet) and (xt or not bc.constant) and self._lam_bc is None:
                 self._lam_bc = torch.zeros(1, dtype=torch.float64, device=self.dev)
-        const = [np.asarray(bc.state) for bc in self.boundary.values() if isinstance(bc, Dirichlet) and bc.constant]
+        const = [np.asarray(bc.state) for bc in self.boundary.values() if isinstance(bc, Dirichlet) and bc.constant and not xt]
         if const:
             b = np.stack(const)
             self._lam_bc_const = max(float(np.max(pde_eval(self.pde, d, b)[1])) for d in range(self.dim))
@@ -496,6 +498,7 @@ class AderDgSolver:
                 if bc.constant:
                     if self._bc_const_done and not xt:
                         continue
+                    lam = self._lam_bc if xt else None
                 else:
                     states = self._dirichlet_states(bc, d, side, [self.time + x * dt for x in xi])
                     lam = self._lam_bc
@@ -516,7 +519,8 @@ class AderDgSolver:
 
     def boundary_eigenvalue(self, lam):
         """lam (1-element device tensor): the CFL eigenvalue with the Dirichlet states taken in -- constant states as a clamp, functions
-        by the eigenvalue the boundary kernel left for the last step (before the first step: f at the face nodes at the current time)."""
+        by the eigenvalue the boundary kernel left for the last step (before the first step: f at the face nodes at the current time).  Where the
+        term set's eigenvalue sees x / t a constant state goes the way of the functions: its eigenvalue at the face nodes, not one number."""
         if self._lam_bc_const is not None:
             lam = lam.clamp(min=self._lam_bc_const)
         if self._lam_bc is not None:
@@ -524,8 +528,11 @@ class AderDgSolver:
                 torch = _torch()
                 self._lam_bc.zero_()
                 for d, side, bc, _, _ in self._bc:
-                    if isinstance(bc, Dirichlet) and not bc.constant:
-                        q = self._dirichlet_states(bc, d, side, [self.time]).reshape(-1, self.nv)
+                    if isinstance(bc, Dirichlet) and (not bc.constant or _sees_position_and_time(self.lib, self.pde)):
+                        if bc.constant:
+                            q = torch.as_tensor(bc.state, dtype=torch.float64, device=self.dev).expand(self.face_positions(d, side).shape[0], self.nv).contiguous()
+                        else:
+                            q = self._dirichlet_states(bc, d, side, [self.time]).reshape(-1, self.nv)
                         self._lam_bc.copy_(torch.maximum(self._lam_bc, _max_eigenvalue_at(self.lib, self.pde, self.dim, q,
                                                                                           self.face_positions(d, side), self.time)))
             lam = _torch().maximum(lam, self._lam_bc)

@@ -327,8 +327,10 @@ int exa_dg_pack_face(exa_dg_plan* plan, const double* trace_dev, int d, int side
  *   EXA_BC_DIRICHLET  ghost = sum_l w_l (q_l, F_d(q_l, x_y, t_l)) over the Gauss time levels t_l = t + xi_l dt of the step (t: the
  *                     time of exa_dg_plan_set_origin_time), with the states states_dev[transverse cell][Nf][N][n_vars] (device) at the
  *                     face nodes x_y (origin + cell size of the last exa_dg_predictor_volume); or, with states_dev NULL, the constant state
- *                     coeff[n_vars] (host) at every node and time.  lambda_dev (device, may be NULL) receives max(*lambda_dev, the largest
- *                     eigenvalue of those states over the directions): not zeroed here, so several faces fold into one scalar.
+ *                     coeff[n_vars] (host) at every node and time: the ghost state is coeff itself (not sum_l w_l coeff), the ghost flux the
+ *                     same sum over the levels where the term set's flux sees x or t, and one evaluation F_d(coeff) where it does not.
+ *                     lambda_dev (device, may be NULL) receives max(*lambda_dev, the largest eigenvalue of those states over the directions,
+ *                     nodes and levels): not zeroed here, so several faces fold into one scalar.
  * Outflow / wall take no states_dev and no lambda_dev; wrong arguments return EXA_ERR_INVALID with a message. */
 #define EXA_BC_OUTFLOW 1
 #define EXA_BC_WALL 2

@@ -117,6 +117,15 @@ def test_numpy_periodic_bcs_reduce_to_the_oracle():
     bcs = {(1, 0): ("dirichlet", (np.take(qR, nc[1] - 1, axis=1), np.take(FR, nc[1] - 1, axis=1))),
            (1, 1): ("dirichlet", (np.take(qL, 0, axis=1), np.take(FL, 0, axis=1)))}
     assert np.max(np.abs(B.step(u, dt, dx, ops, A.Euler(), bcs) - want)) <= 1e-14 * np.max(np.abs(want))
+    assert np.array_equal(B.step(u, dt, dx, ops, A.Euler(), {}), want)                      # (the same operations in the same order)
+    # the form with x, t and an ncp: no condition == step_xt, bit for bit
+    pytest.importorskip("sympy")
+    from tests.dg_boundary_cases import ORIGIN, T0, coupled_system
+    o = coupled_system(3)[1]
+    v = 1.0 + 0.3 * np.random.default_rng(3).random(tuple(nc) + (N,) * dim + (3,))
+    want = A.step_xt(v, dt, dx, ops, o, t=T0, origin=ORIGIN)
+    assert np.array_equal(B.step_xt(v, dt, dx, ops, o, {}, t=T0, origin=ORIGIN), want)
+    assert np.array_equal(B.step_xt(v, dt, dx, ops, o, {}, t=T0, origin=ORIGIN, n_it=N - 1), A.step_xt(v, dt, dx, ops, o, t=T0, origin=ORIGIN, n_it=N - 1))
 
 
 def test_numpy_outflow_of_a_uniform_state_is_steady():

@@ -1,6 +1,8 @@
 """ADER-DG domain boundaries on the GPU (exa_dg_boundary_ghost, AderDgSolver(boundary=...)): stage B with boundary ghosts against the numpy
-restatement for every kind, the outflow ghost against exa_dg_pack_face, walls against the mirrored periodic box, a closed box, exact
-boundary data at full order, sharded blocks, the subcell limiter and the CFL step of run()."""
+restatement for every kind at DG_TOL of the increment (Euler rows, and rows whose terms see x and t with an ncp; tables and references in
+tests/dg_boundary_cases.py, their CPU check in tests/test_dg_boundary_reference.py), run() against its replay, the outflow ghost against
+exa_dg_pack_face, walls against the mirrored periodic box, a closed box, exact boundary data at full order, sharded blocks, the subcell
+limiter and the CFL step of run()."""
 import ctypes as CT
 import os
 import subprocess
@@ -11,13 +13,13 @@ import pytest
 
 from oracle import aderdg_numpy as A
 from oracle.dg_operators import operators
+from tests import dg_boundary_cases as BC
 from tests import dg_boundary_numpy as B
-from tests.util import cfl_dt, dg_err, euler_dg_state
+from tests.dg_boundary_cases import smooth_state
+from tests.util import DG_TOL, assert_dg_parity, cfl_dt, dg_err, euler_dg_state
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-EULER_SIGN = {a: np.where(np.arange(5) == 1 + a, -1.0, 1.0) for a in range(3)}
-Q_IN = np.array([1.3, 0.4, -0.2, 0.1, 3.1])                      # a constant Dirichlet state
 
 
 @pytest.fixture(scope="module")
@@ -28,17 +30,6 @@ def exa():
     return solvers
 
 
-def smooth_state(X, t):
-    """An admissible Euler state that varies in space and time; numpy arrays or device tensors [..., 3] -> [..., 5]."""
-    import torch
-    lib = torch if isinstance(X, torch.Tensor) else np
-    x, y, z = X[..., 0], X[..., 1], X[..., 2]
-    rho = 1.0 + 0.2 * lib.sin(2.0 * x + y - 0.5 * z + 3.0 * t)
-    vx, vy, vz = 0.3 * lib.cos(x - y + t), 0.2 * lib.sin(y + z - t), -0.1 + 0.05 * x
-    p = 1.0 + 0.1 * lib.cos(x + z + 2.0 * t)
-    return lib.stack([rho, rho * vx, rho * vy, rho * vz, p / 0.4 + 0.5 * rho * (vx * vx + vy * vy + vz * vz)], -1)
-
-
 def density_wave(X, t, d=3):
     """rho = 1 + 0.2 sin(2 pi (x + y + z - 3 t)), velocity (1, 1, 1), p = 1: pure advection (tests/test_gpu_parity.py's exact solution)."""
     import torch
@@ -47,54 +38,88 @@ def density_wave(X, t, d=3):
     return lib.stack([rho, rho, rho, rho, 1 / 0.4 + 0.5 * rho * d], -1)
 
 
-def _solver_bc(exa, kinds):
-    """kinds {(axis, side): name} -> the solver's boundary dict"""
-    out = {}
-    for key, k in kinds.items():
-        out[key] = {"outflow": exa.Outflow(), "wall": exa.Wall(), "const": exa.Dirichlet(Q_IN), "func": exa.Dirichlet(smooth_state)}[k]
+def _solver(exa, c, **kw):
+    """the AderDgSolver of a tests/dg_boundary_cases.py Case: its box, origin, start time and boundary dict"""
+    cond = {"outflow": lambda a: exa.Outflow(), "wall": lambda a: exa.Wall() if c.table == "euler" else exa.Wall(c.sign(a)),
+            "const": lambda a: exa.Dirichlet(c.const), "func": lambda a: exa.Dirichlet(c.func)}
+    if c.table == "xt":
+        kw = dict(dict(pde=c.sympy_pde.register(), n_vars=3), **kw)
+    return exa.AderDgSolver(c.dim, c.N, c.nc, dx=c.dx, stage_a=c.stage_a, n_picard=c.n_picard, origin=c.origin, time=c.t0,
+                            boundary={key: cond[k](key[0]) for key, k in c.kinds.items()}, **kw)
+
+
+def _euler_params():
+    """(the five rows that were here before the tables keep their ids)"""
+    out = []
+    for row, kind in BC.EULER_CASES:
+        i = BC.EULER_ROWS.index(row)
+        old = i < len(BC.PARITY_CASES)
+        out.append(pytest.param(row, kind, id="%d-%d-nc%d-%s-%s" % (row[0], row[1], i, row[3] if old else "%s%d" % (row[3], row[4]), kind)))
     return out
 
 
-def _oracle_bc(kinds, nc, N, ops, dx, dt):
-    out = {}
-    for (a, side), k in kinds.items():
-        if k == "outflow":
-            out[(a, side)] = ("outflow",)
-        elif k == "wall":
-            out[(a, side)] = ("wall", EULER_SIGN[a])
-        else:
-            X = B.face_positions(nc, N, ops, dx, a, side)
-            out[(a, side)] = ("dirichlet", B.dirichlet_ghost(Q_IN if k == "const" else smooth_state, A.Euler(), X, a, 0.0, dt, ops,
-                                                             constant=k == "const"))
-    return out
-
-
-KIND_SETS = {
-    "outflow": lambda dim: {(a, s): "outflow" for a in range(dim) for s in range(2)},
-    "wall": lambda dim: {(a, s): "wall" for a in range(dim) for s in range(2)},
-    "const": lambda dim: {(a, s): "const" for a in range(dim) for s in range(2)},
-    "func": lambda dim: {(a, s): "func" for a in range(dim) for s in range(2)},
-    "mixed": lambda dim: {(0, 0): "func", (0, 1): "outflow", (1, 0): "wall", (1, 1): "const"},     # (axis 2, if any: periodic)
-}
-PARITY_CASES = [(2, 4, (4, 3), "auto"), (3, 3, (3, 2, 2), "auto"), (3, 6, (2, 3, 2), "lds"), (3, 6, (2, 3, 2), "reg"), (3, 8, (2, 2, 2), "auto")]
-
-
-@pytest.mark.parametrize("kind", sorted(KIND_SETS))
-@pytest.mark.parametrize("dim,N,nc,stage_a", PARITY_CASES)
-def test_stage_b_with_boundary_ghosts_vs_numpy(exa, dim, N, nc, stage_a, kind):
-    ops = operators(N)
-    u = euler_dg_state(tuple(nc) + (N,) * dim, seed=5)
-    dx = [0.7 / c for c in nc]
-    dt = cfl_dt(u, dx, dim, N, cfl=0.6)
-    kinds = KIND_SETS[kind](dim)
-    s = exa.AderDgSolver(dim, N, nc, dx=dx, stage_a=stage_a, boundary=_solver_bc(exa, kinds))
-    s.upload(u)
-    s.step(dt)
-    want = B.step(u, dt, dx, ops, A.Euler(), _oracle_bc(kinds, nc, N, ops, dx, dt))
-    e = dg_err(s.download(), want, u)
+@pytest.mark.parametrize("row,kind", _euler_params())
+def test_stage_b_with_boundary_ghosts_vs_numpy(exa, row, kind):
+    """One step at CFL 0.9 of every Euler row and kind set against the restatement, to DG_TOL of the increment; the restatement with one Picard
+    iteration less is seen (tests/test_dg_boundary_reference.py: and so is every other mutant of the row)."""
+    c = BC.get_case("euler", row, kind)
+    s = _solver(exa, c)
+    s.upload(c.u)
+    s.step(c.dt)
+    want = c.state()
+    got = s.download()
+    e = dg_err(got, want, c.u)
+    print("euler %s: dg_err %.3e" % (BC.case_id((row, kind)), e))
+    assert_dg_parity(got, want, c.u, c.state("picard") if c.n_it > 0 else None, tol=DG_TOL, what="euler " + BC.case_id((row, kind)))
     assert e <= 1e-10, (kind, e)
     # the same data periodic differs from it by far more than the tolerance: the ghosts were used
-    assert dg_err(A.step(u, dt, dx, ops, A.Euler()), want, u) > 1e-6
+    ops = operators(c.N)
+    periodic = A.step_single_stage(c.u, c.dt, c.dx, ops, A.Euler()) if c.n_it == 0 else A.step(c.u, c.dt, c.dx, ops, A.Euler())
+    assert dg_err(periodic, want, c.u) > 1e-6
+
+
+@pytest.mark.parametrize("row,kind", [pytest.param(r, k, id=BC.case_id((r, k))) for r, k in BC.XT_CASES])
+def test_xt_term_set_with_boundary_ghosts_vs_numpy(exa, row, kind):
+    """Term sets whose flux, eigenvalue and ncp see x and t, on a bounded box away from the origin: two steps of different size from t = 0.4.  The
+    boundary kernel places the face nodes itself (transverse axes, normal coordinate, level times) for the flux of the Dirichlet data -- of a
+    function and of a constant state -- and for the eigenvalue it leaves to run(); stage B reads q+ of the ncp's jump term from the ghost."""
+    c = BC.get_case("xt", row, kind)
+    s = _solver(exa, c)
+    assert s.lib.exa_pde_flags(s.pde) == (1 if c.with_xt else 0) + (2 if c.with_ncp else 0)
+    s.upload(c.u)
+    t = c.t0
+    for dt in c.dts:
+        s.step(dt)
+        t += dt
+    assert abs(s.time - t) < 1e-15
+    what = "xt " + BC.case_id((row, kind))
+    e, em = assert_dg_parity(s.download(), c.state(dts=c.dts), c.u, c.state("picard", dts=c.dts), tol=DG_TOL, what=what)
+    # the eigenvalue the boundary kernel left: of the Dirichlet states of the LAST step, over levels, face nodes and directions (a constant
+    # state's too where the eigenvalue sees x / t; elsewhere it is a host clamp).  test_cfl_launch_same_u_and_exact_maximum compares two device
+    # evaluations and can ask for equal bits; this one compares the device with numpy, whose sine and whose roundings are not the device's: the
+    # eigenvalue |a_d + 3/10 sin(2 x + t)| + |q0| / 5 is eight rounded operations on terms no larger than the result (the datum's own sine included;
+    # the device may contract 2 x + t and the products into FMAs), each within one unit in the last place -- 8 ulp.  Measured: equal in 11 of 12 cases,
+    # one ulp (2.2e-16) in the twelfth.  The levels of the step before, the midpoint alone or the origin left out move it by 2e-5 to 0.15.
+    want_lam = c.dirichlet_eigenvalue(c.t0 + c.dts[0], c.dts[1], kinds=("func", "const") if c.with_xt else ("func",))
+    got_lam = float(s._lam_bc[0])
+    print("%s: dg_err %.3e, mutant %.3e, lam_bc %.17g, restatement %.17g, diff %.3e" % (what, e, em, got_lam, want_lam, got_lam - want_lam))
+    assert abs(got_lam - want_lam) <= 8 * np.finfo(np.float64).eps * want_lam, (got_lam, want_lam)
+
+
+@pytest.mark.parametrize("table,row,kind", BC.RUN_CASES)
+def test_run_on_a_bounded_box_equals_the_replay(exa, table, row, kind):
+    """run(t_end, cfl) for about 2.5 steps against the loop replayed on the restatement: the eigenvalue of the state and of the Dirichlet data, then
+    the step (tests/dg_boundary_cases.py Case.replay).  In the x / t row the constant state's eigenvalue at the face nodes sets every step."""
+    c = BC.get_case(table, row, kind)
+    t_end = c.t_end()
+    steps, t, want = c.replay(t_end)
+    s = _solver(exa, c)
+    s.upload(c.u)
+    n = s.run(t_end, cfl=BC.RUN_CFL)
+    print("run %s %s: steps %d (replay %d), time - replay %.3e" % (table, BC.case_id((row, kind)), n, steps, s.time - t))
+    assert n == steps, (n, steps)
+    assert abs(s.time - t) <= 1e-14, (s.time, t)
+    assert_dg_parity(s.download(), want, c.u, c.replay(t_end, mutant="picard")[2], tol=DG_TOL, what="run %s %s" % (table, BC.case_id((row, kind))))
 
 
 @pytest.mark.parametrize("dim,N,nc", [(2, 4, (4, 3)), (3, 6, (2, 3, 4)), (3, 5, (3, 2, 2))])
@@ -372,3 +397,50 @@ def test_sharded_walls_equal_the_single_block(tmp_path, N, nc):
 def test_sharded_walls_over_rccl_send_recv_to_self(tmp_path):
     """one rank on RCCL, its own neighbour along the walled axis: the wrap layers travel, the boundary ghosts are what stage B reads"""
     _run_ranks(tmp_path, SHARD_WORKER % dict(root=ROOT, N=6, nc=(3, 2, 2), pdims=[1, 1, 1], selfx=(0,), backend="nccl", gloo=False), 1)
+
+
+SHARD_XT_WORKER = r'''
+import os, sys
+sys.path.insert(0, %(root)r)
+import numpy as np, torch, torch.distributed as dist
+from exahype_amd import solvers as exa
+from tests import dg_boundary_cases as BC
+from tests.util import assert_dg_parity, assert_shard_equals_whole_block
+rank, world = int(os.environ["RANK"]), int(os.environ["WORLD_SIZE"])
+torch.cuda.set_device(0)
+dist.init_process_group("gloo", rank=rank, world_size=world)
+dim, N, nc, pdims = BC.SHARDED_XT_BC_CASE
+c = BC.sharded_xt_bc_case()                                     # the WHOLE block: c.nc = nc * pdims
+part = exa.CartesianPartition(world, rank, dim, pdims)
+pid = c.sympy_pde.register()
+bc = lambda: {key: exa.Dirichlet(c.func if k == "func" else c.const) for key, k in c.kinds.items()}
+s = exa.AderDgSolver(dim, N, nc, pde=pid, n_vars=3, dx=c.dx, part=part, backend_is_gloo=True, origin=c.origin, time=c.t0, boundary=bc())
+assert s.halo is not None
+sl = tuple(slice(part.coords[a] * nc[a], (part.coords[a] + 1) * nc[a]) for a in range(3))
+s.upload(c.u[sl])
+whole = exa.AderDgSolver(dim, N, c.nc, pde=pid, n_vars=3, dx=c.dx, origin=c.origin, time=c.t0, boundary=bc())
+whole.upload(c.u)
+for dt in c.dts:
+    s.step(dt)
+    whole.step(dt)
+torch.cuda.synchronize()
+got, block = s.download(), whole.download()
+failed = None
+try:
+    assert abs(s.time - whole.time) < 1e-15
+    assert_shard_equals_whole_block(got, block[sl], c.u[sl], s, whole, "x/t Dirichlet faces N %%d, rank %%d" %% (N, rank))
+    assert_dg_parity(block, c.state(dts=c.dts), c.u, c.state("picard", dts=c.dts), what="x/t Dirichlet faces, whole block (rank %%d)" %% rank)
+except AssertionError as e:
+    failed = e
+dist.barrier(); dist.destroy_process_group()                    # (leave together: a rank that failed alone would keep the others waiting)
+print("rank", rank, "bit-equal", np.array_equal(got, block[sl]))
+if failed is not None:
+    raise failed
+'''
+
+
+def test_sharded_dirichlet_faces_of_an_xt_term_set_equal_the_single_block(tmp_path):
+    """two ranks over gloo sharing cuda:0, the x / t + ncp set: the Dirichlet function on both x faces (one per rank) and on the low y face, whose
+    nodes on rank 1 lie at that shard's offset, the constant state on the high z face; three steps of different size.  Every shard against the
+    whole block, the whole block against the restatement to DG_TOL."""
+    _run_ranks(tmp_path, SHARD_XT_WORKER % dict(root=ROOT), 2)
