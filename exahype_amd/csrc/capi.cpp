@@ -7,6 +7,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <deque>
 #include <new>
 #include <vector>
 #include <dlfcn.h>
@@ -35,73 +36,47 @@ void set_error(const char* fmt, ...) {
 
 const DgLaunchTable *dg_table_2_0(), *dg_table_2_1(), *dg_table_2_2(), *dg_table_3_1(), *dg_table_3_2();
 
-// ---- run-time registered PDE term sets (side libraries generated from SymPy expressions) -------------
-struct UserPde {
-    void* handle;
-    const DgLaunchTable* dg[4];
-    int nv;
-    int flags;             // EXA_PDE_FLAG_*
-    int (*fv)(int, int, int, int, int, int, long, double*, double, double, const long*, void*, double*, const double*, double, const void*);
-    int (*fvmax)(int, int, int, int, int, long, const double*, double*, void*, const double*, double, double);
-    int (*ev)(int, long, int, const double*, double*, double*, void*, const double*, double);
-    // the term set's own a-posteriori detector (EXA_PDE_FLAG_ADMISSIBLE; lim_user.hip) and its watched-variable count
-    int k_dmp;
-    int (*lim_snap)(int, int, long, const double*, double*, double*, void*);
-    int (*lim_det)(int, int, const long*, const double*, const double*, const double* const*, const int*, double, double, double, unsigned char*, void*);
-    // the term set's instantiation of the limiter's conservative interface (EXA_PDE_FLAG_CONSERVATIVE; lim_conserve_user.hip)
-    int (*lim_flux)(int, int, const double*, const long*, long, double*, const double*, void*);
-    int (*lim_corr)(int, int, const long*, double*, const double*, const long*, long, const unsigned char*, const int*, const double*, double, const double*,
-                    const double*, const double*, const double*, void*);
-    // the term set's instantiation of the MUSCL-Hancock patch update (EXA_PDE_FLAG_MUSCL_HANCOCK; fv_muscl_user.hip)
-    int (*fvm)(int, int, int, int, int, long, double*, double, double, const long*, void*, double*);
-    // ... and of its grid step on halo-less arrays (exa_user_fv_muscl_grid_launch); null in a library built before that entry existed
-    int (*fvmg)(int, int, int, int, long, const double*, double*, double, double, const void*, void*);
-    // ... and of the plane-streaming form of the 3-D update (exa_user_fv_muscl_stream_launch); null in a library built before that entry existed
-    int (*fvms)(int, int, int, int, long, double*, double, double, const long*, void*, double*);
-};
-static std::vector<UserPde> g_user;
+// ---- the term sets: built in (ids 0 .. 2) or registered at run time (ids >= 100; side libraries generated from SymPy expressions).  Where a term
+// set's kernels are found is decided here and in exa_register_pde; everything downstream holds a PdeKernels* -----------------------------------
+static std::deque<PdeKernels> g_user;       // (a deque: the plans keep pointers to its entries)
 
-int user_fv_launch(int pde, int mode, int dim, int P, int H, int n_real, int n_aux, long n_patches, double* Q, double dt,
-                   double h, const long* slot, hipStream_t s, double* out, const double* centre, double t, const FvGridArgs* grid) {
-    if (pde - 100 >= (int)g_user.size() || !g_user[pde - 100].fv) { set_error("pde %d is not registered", pde); return -1; }
-    return g_user[pde - 100].fv(mode, dim, P, H, n_real, n_aux, n_patches, Q, dt, h, slot, (void*)s, out, centre, t, grid);
-}
-int user_fv_muscl_launch(int pde, int dim, int P, int H, int n_real, int n_aux, long n_patches, double* Q, double dt, double h, const long* slot,
-                         hipStream_t s, double* out) {
-    if (pde - 100 >= (int)g_user.size() || !g_user[pde - 100].fvm) { set_error("pde %d carries no MUSCL-Hancock kernel", pde); return -1; }
-    return g_user[pde - 100].fvm(dim, P, H, n_real, n_aux, n_patches, Q, dt, h, slot, (void*)s, out);
-}
-int user_fv_muscl_stream_launch(int pde, int P, int H, int n_real, int n_aux, long n_patches, double* Q, double dt, double h, const long* slot,
-                                hipStream_t s, double* out) {
-    if (pde - 100 >= (int)g_user.size() || !g_user[pde - 100].fvms) { set_error("pde %d carries no streamed MUSCL-Hancock kernel", pde); return -1; }
-    return g_user[pde - 100].fvms(P, H, n_real, n_aux, n_patches, Q, dt, h, slot, (void*)s, out);
-}
-int user_fv_muscl_grid_launch(int pde, int dim, int P, int n_real, int n_aux, long n_patches, const double* Q, double* out, double dt, double h,
-                              const FvMusclGrid* grid, hipStream_t s) {
-    if (pde - 100 >= (int)g_user.size() || !g_user[pde - 100].fvmg) {
-        set_error("pde %d: its side library exports no exa_user_fv_muscl_grid_launch (built before the MUSCL-Hancock grid step existed); rebuild the "
-                  "term set (SympyPDE(..., muscl_hancock=True).build(force=True)) or use the two-pass form on the array with halo", pde);
-        return -1;
+const PdeKernels* pde_kernels(int pde) {
+    // nv: EulerRef2D evolves (rho, rho u, rho v, E); k_dmp: the Euler-layout criterion of limiter.hip watches density and energy
+    static const struct Builtin {
+        PdeKernels tab[3] = {{PDE_KERNELS_ABI, 4, 0, 2, 2}, {PDE_KERNELS_ABI, 5, 0, 3, 2}, {PDE_KERNELS_ABI, 1, 0, 3, 2}};
+        Builtin() {
+            tab[0].dg[2] = dg_table_2_0();
+            tab[1].dg[2] = dg_table_2_1(); tab[1].dg[3] = dg_table_3_1();
+            tab[2].dg[2] = dg_table_2_2(); tab[2].dg[3] = dg_table_3_2();
+            fv_fill_builtin(tab);
+            fv_muscl_fill_builtin(tab);
+            limiter_fill_builtin(tab);
+        }
+    } builtin;
+    if (pde >= 100) {
+        if (pde - 100 < (int)g_user.size()) return &g_user[pde - 100];
+        set_error("pde %d is not registered", pde);
+        return nullptr;
     }
-    return g_user[pde - 100].fvmg(dim, P, n_real, n_aux, n_patches, Q, out, dt, h, grid, (void*)s);
-}
-int user_fv_maxeig(int pde, int dim, int P, int H, int n_real, int n_aux, long n_patches, const double* Q, double* lam, hipStream_t s,
-                   const double* centre, double t, double h) {
-    if (pde - 100 >= (int)g_user.size() || !g_user[pde - 100].fvmax) { set_error("pde %d is not registered", pde); return -1; }
-    return g_user[pde - 100].fvmax(dim, P, H, n_real, n_aux, n_patches, Q, lam, (void*)s, centre, t, h);
-}
-int user_pde_eval(int pde, int normal, long n, int stride, const double* Q, double* F, double* lam, hipStream_t s, const double* X, double t) {
-    if (pde - 100 >= (int)g_user.size() || !g_user[pde - 100].ev) { set_error("pde %d is not registered", pde); return -1; }
-    return g_user[pde - 100].ev(normal, n, stride, Q, F, lam, (void*)s, X, t);
+    if (pde >= 0 && pde <= 2) return &builtin.tab[pde];
+    set_error("unknown pde %d", pde);
+    return nullptr;
 }
 
 const DgLaunchTable* dg_launch_table(int dim, int pde) {
-    if (pde >= 100) return (pde - 100 < (int)g_user.size() && dim >= 2 && dim <= 3) ? g_user[pde - 100].dg[dim] : nullptr;
-    if (dim == 2 && pde == 0) return dg_table_2_0();
-    if (dim == 2 && pde == 1) return dg_table_2_1();
-    if (dim == 2 && pde == 2) return dg_table_2_2();
-    if (dim == 3 && pde == 1) return dg_table_3_1();
-    if (dim == 3 && pde == 2) return dg_table_3_2();
+    const PdeKernels* k = pde_kernels(pde);
+    return (k && dim >= 2 && dim <= 3) ? k->dg[dim] : nullptr;
+}
+
+// A slot of a term set's table is tested through these and nowhere else: null sets the error.
+template <class F> static F slot_or_error(F f, int pde, const char* what) {
+    if (!f) set_error("pde %d carries no %s", pde, what);
+    return f;
+}
+static auto fv_muscl_slot(const PdeKernels* k, int pde) -> decltype(k->fv_muscl) {
+    if (k->fv_muscl) return k->fv_muscl;
+    if (pde == EXA_PDE_EULER_REF2D) set_error("EXA_FV_MUSCL_HANCOCK: EULER_REF2D is the reference's quirk set (F[4] is never written); use EXA_PDE_EULER");
+    else set_error("EXA_FV_MUSCL_HANCOCK: pde %d was generated without the MUSCL-Hancock kernel; build it with SympyPDE(..., muscl_hancock=True)", pde);
     return nullptr;
 }
 
@@ -115,12 +90,14 @@ struct exa_fv_plan {
     int device, mode, dim, P, H, n_real, n_aux, pde;
     long n_patches, count;
     int streamed;          // EXA_FV_MUSCL_HANCOCK, 3-D: the plane-streaming kernel serves the plan (exa_fv_plan_create_streamed)
+    const PdeKernels* k;   // the term set's kernels (pde_kernels(pde) at creation)
 };
 
 struct exa_dg_plan {
     int device, dim, N, nv, pde, n_it;
     long nc[3], ncells;
-    const DgLaunchTable* tab;
+    const PdeKernels* k;   // the term set's kernels (pde_kernels(pde) at creation) and ...
+    const DgLaunchTable* tab;      // ... k->dg[dim]
     DgOpsHost ops;
     double idx[3];         // 1 / dx of the last stage A: where exa_dg_boundary_ghost places the face nodes of a Dirichlet datum
 };
@@ -156,8 +133,9 @@ int exa_register_pde(const char* library_path, int* pde_id) {
     if (!library_path || !pde_id) { set_error("exa_register_pde: NULL argument"); return EXA_ERR_INVALID; }
     void* h = dlopen(library_path, RTLD_NOW | RTLD_LOCAL);
     if (!h) { set_error("exa_register_pde: %s", dlerror()); return EXA_ERR_INVALID; }
-    UserPde u{};
-    u.handle = h;
+    PdeKernels u{};
+    u.abi = PDE_KERNELS_ABI;
+    u.k_dmp = 2;                                                   // (without a detector unit: the Euler-layout criterion of limiter.hip)
     typedef const void* (*tab_fn)();
     for (int d = 2; d <= 3; d++) {
         char name[64];
@@ -165,53 +143,32 @@ int exa_register_pde(const char* library_path, int* pde_id) {
         tab_fn f = (tab_fn)dlsym(h, name);
         u.dg[d] = f ? static_cast<const DgLaunchTable*>(f()) : nullptr;
     }
-    int (*nvf)() = (int (*)())dlsym(h, "exa_user_nv");
-    u.fv = (decltype(u.fv))dlsym(h, "exa_user_fv_launch");
-    u.fvmax = (decltype(u.fvmax))dlsym(h, "exa_user_fv_maxeig");
-    u.ev = (decltype(u.ev))dlsym(h, "exa_user_pde_eval");
-    if (!nvf || (!u.dg[2] && !u.dg[3] && !u.fv)) { dlclose(h); set_error("%s exports no exahype_amd PDE entry points", library_path); return EXA_ERR_INVALID; }
-    u.nv = nvf();
-    int (*flf)() = (int (*)())dlsym(h, "exa_user_pde_flags");
-    u.flags = flf ? flf() : 0;
-    if (u.flags & EXA_PDE_FLAG_ADMISSIBLE) {
-        int (*kf)() = (int (*)())dlsym(h, "exa_user_lim_k_dmp");
-        u.lim_snap = (decltype(u.lim_snap))dlsym(h, "exa_user_lim_snapshot");
-        u.lim_det = (decltype(u.lim_det))dlsym(h, "exa_user_lim_detect");
-        if (!kf || !u.lim_snap || !u.lim_det) {
+    // one filler per unit the library was built with (fv_rusanov.hip -- in every library: it brings nv, flags and max_dim --, lim_user.hip,
+    // lim_conserve_user.hip, fv_muscl_user.hip); a filler built for another table layout writes nothing and returns its PDE_KERNELS_ABI
+    static const char* const fillers[] = {"exa_user_fill_fv", "exa_user_fill_lim", "exa_user_fill_lim_conserve", "exa_user_fill_fv_muscl"};
+    for (const char* name : fillers) {
+        int (*fill)(PdeKernels*) = (int (*)(PdeKernels*))dlsym(h, name);
+        const int abi = fill ? fill(&u) : 0;
+        if (abi != 0) {
             dlclose(h);
-            set_error("%s carries an admissibility criterion but exports no exa_user_lim_snapshot / exa_user_lim_detect", library_path);
-            return EXA_ERR_INVALID;
-        }
-        u.k_dmp = kf();
-    }
-    if (u.flags & EXA_PDE_FLAG_CONSERVATIVE) {
-        u.lim_flux = (decltype(u.lim_flux))dlsym(h, "exa_user_lim_face_flux");
-        u.lim_corr = (decltype(u.lim_corr))dlsym(h, "exa_user_lim_interface_correct");
-        if (!u.lim_flux || !u.lim_corr) {
-            dlclose(h);
-            set_error("%s asks for the conservative DG / FV interface but exports no exa_user_lim_face_flux / exa_user_lim_interface_correct", library_path);
+            set_error("%s was built for kernel table ABI %d, this libexahype_hip has %d: rebuild the term set (SympyPDE(...).build(force=True))", library_path,
+                      abi, PDE_KERNELS_ABI);
             return EXA_ERR_INVALID;
         }
     }
-    if (u.flags & EXA_PDE_FLAG_MUSCL_HANCOCK) {
-        u.fvm = (decltype(u.fvm))dlsym(h, "exa_user_fv_muscl_launch");
-        if (!u.fvm) {
-            dlclose(h);
-            set_error("%s asks for the MUSCL-Hancock patch update but exports no exa_user_fv_muscl_launch", library_path);
-            return EXA_ERR_INVALID;
-        }
-        u.fvmg = (decltype(u.fvmg))dlsym(h, "exa_user_fv_muscl_grid_launch");      // (optional: older cached builds have none)
-        u.fvms = (decltype(u.fvms))dlsym(h, "exa_user_fv_muscl_stream_launch");    // (optional likewise)
-    }
+    const char* missing = nullptr;
+    if (!u.fv) missing = "exports no exahype_amd PDE entry points (exa_user_fill_fv; a library from before the kernel table: rebuild the term set)";
+    else if ((u.flags & EXA_PDE_FLAG_ADMISSIBLE) && (!u.lim_snapshot || !u.lim_detect)) missing = "carries an admissibility criterion but no detector unit (exa_user_fill_lim)";
+    else if ((u.flags & EXA_PDE_FLAG_CONSERVATIVE) && (!u.lim_face_flux || !u.lim_interface_correct))
+        missing = "asks for the conservative DG / FV interface but has no such unit (exa_user_fill_lim_conserve)";
+    else if ((u.flags & EXA_PDE_FLAG_MUSCL_HANCOCK) && !u.fv_muscl) missing = "asks for the MUSCL-Hancock patch update but has no such unit (exa_user_fill_fv_muscl)";
+    if (missing) { dlclose(h); set_error("%s %s", library_path, missing); return EXA_ERR_INVALID; }
     g_user.push_back(u);
     *pde_id = 100 + (int)g_user.size() - 1;
     return EXA_OK;
 }
 
-int exa_pde_flags(int pde) {
-    if (pde >= 100) return (pde - 100 < (int)g_user.size()) ? g_user[pde - 100].flags : 0;
-    return 0;
-}
+int exa_pde_flags(int pde) { return (pde >= 100 && pde - 100 < (int)g_user.size()) ? g_user[pde - 100].flags : 0; }
 
 int exa_pde_eval_device(int pde, int normal, long n, int stride, const double* Q_dev, double* F_dev, double* lambda_dev,
                         void* stream) {
@@ -220,17 +177,13 @@ int exa_pde_eval_device(int pde, int normal, long n, int stride, const double* Q
 
 int exa_pde_eval_device_at(int pde, int normal, long n, int stride, const double* Q_dev, const double* x_dev, double t, double* F_dev,
                            double* lambda_dev, void* stream) {
-    if (pde >= 100) {
-        if (normal < 0 || normal > 2 || n < 0 || stride < 1 || !Q_dev) { set_error("exa_pde_eval_device: bad argument"); return EXA_ERR_INVALID; }
-        return pde_eval_launch(pde, normal, n, stride, Q_dev, F_dev, lambda_dev, (hipStream_t)stream, x_dev, t);
-    }
-    if (pde < 0 || pde > 2 || normal < 0 || normal > 2 || n < 0 || stride < 1 || !Q_dev) {
-        set_error("exa_pde_eval_device: bad argument");
-        return EXA_ERR_INVALID;
-    }
+    if (normal < 0 || normal > 2 || n < 0 || stride < 1 || !Q_dev) { set_error("exa_pde_eval_device: bad argument"); return EXA_ERR_INVALID; }
+    const PdeKernels* k = pde_kernels(pde);
+    if (!k) return EXA_ERR_INVALID;
     if (pde == EXA_PDE_EULER_REF2D && (normal > 1 || stride < 4)) { set_error("EULER_REF2D needs normal < 2 and stride >= 4"); return EXA_ERR_INVALID; }
     if (pde == EXA_PDE_EULER && stride < 5) { set_error("EULER needs stride >= 5"); return EXA_ERR_INVALID; }
-    return pde_eval_launch(pde, normal, n, stride, Q_dev, F_dev, lambda_dev, (hipStream_t)stream, x_dev, t);
+    const auto eval = slot_or_error(k->pde_eval, pde, "flux / eigenvalue kernel");
+    return eval ? eval(normal, n, stride, Q_dev, F_dev, lambda_dev, x_dev, t, (hipStream_t)stream) : EXA_ERR_INVALID;
 }
 
 /* ---- FV ---------------------------------------------------------------------- */
@@ -262,20 +215,12 @@ static int fv_plan_create(int device, int mode, int dim, int patch_size, int hal
     if (n_real < 1 || n_real > 8 || n_aux < 0 || n_patches < 0) { set_error("n_real must be 1..8, n_aux >= 0, n_patches >= 0"); return EXA_ERR_INVALID; }
     if (pde == EXA_PDE_EULER_REF2D && (dim != 2 || n_real < 4)) { set_error("EULER_REF2D is the reference's 2-D term set (n_real >= 4)"); return EXA_ERR_INVALID; }
     if (pde == EXA_PDE_EULER && n_real < 5) { set_error("EULER needs n_real >= 5"); return EXA_ERR_INVALID; }
-    if (pde >= 100) {
-        if (pde - 100 >= (int)g_user.size()) { set_error("pde %d is not registered", pde); return EXA_ERR_INVALID; }
-        if (n_real < g_user[pde - 100].nv) { set_error("pde %d evolves %d variables; n_real = %d", pde, g_user[pde - 100].nv, n_real); return EXA_ERR_INVALID; }
-    } else if (pde < 0 || pde > 2) { set_error("unknown pde %d", pde); return EXA_ERR_INVALID; }
+    const PdeKernels* k = pde_kernels(pde);
+    if (!k) return EXA_ERR_INVALID;
+    if (n_real < k->nv) { set_error("pde %d evolves %d variables; n_real = %d", pde, k->nv, n_real); return EXA_ERR_INVALID; }
     int streamed = 0;
     if (mode == EXA_FV_MUSCL_HANCOCK) {
-        if (pde == EXA_PDE_EULER_REF2D) {
-            set_error("EXA_FV_MUSCL_HANCOCK: EULER_REF2D is the reference's quirk set (F[4] is never written); use EXA_PDE_EULER");
-            return EXA_ERR_INVALID;
-        }
-        if (pde >= 100 && !(g_user[pde - 100].flags & EXA_PDE_FLAG_MUSCL_HANCOCK)) {
-            set_error("EXA_FV_MUSCL_HANCOCK: pde %d was generated without the MUSCL-Hancock kernel; build it with SympyPDE(..., muscl_hancock=True)", pde);
-            return EXA_ERR_INVALID;
-        }
+        if (!fv_muscl_slot(k, pde)) return EXA_ERR_INVALID;
         FvMusclPlan pl;
         const bool resident = patch_size <= 1024 && fv_muscl_plan(dim, patch_size, n_real, n_real + n_aux, &pl);
         if (patch_size > 1024) pl.lds = (size_t)-1;
@@ -286,11 +231,6 @@ static int fv_plan_create(int device, int mode, int dim, int patch_size, int hal
                 set_error("EXA_FV_MUSCL_HANCOCK: a patch of %d^3 volumes with %d + %d variables needs %zu bytes of LDS with the whole window resident and "
                           "%zu bytes plane by plane (five window planes, three predictor planes), %zu bytes are available", patch_size, n_real, n_aux,
                           pl.lds, ps.lds, FV_MUSCL_LDS_AVAILABLE);
-                return EXA_ERR_INVALID;
-            }
-            if (pde >= 100 && !g_user[pde - 100].fvms) {
-                set_error("EXA_FV_MUSCL_HANCOCK: pde %d: its side library exports no exa_user_fv_muscl_stream_launch (built before the plane-streaming "
-                          "kernel existed); rebuild the term set (SympyPDE(..., muscl_hancock=True).build(force=True))", pde);
                 return EXA_ERR_INVALID;
             }
             streamed = 1;
@@ -310,6 +250,7 @@ static int fv_plan_create(int device, int mode, int dim, int patch_size, int hal
     p->n_real = n_real; p->n_aux = n_aux; p->pde = pde; p->n_patches = n_patches;
     p->count = n_patches * lpow(patch_size + 2 * halo_size, dim) * (n_real + n_aux);
     p->streamed = streamed;
+    p->k = k;
     *plan = p;
     return EXA_OK;
 }
@@ -330,11 +271,14 @@ int exa_fv_plan_destroy(exa_fv_plan* plan) { delete plan; return EXA_OK; }
 
 long exa_fv_q_count(const exa_fv_plan* plan) { return plan ? plan->count : 0; }
 
-// the second-order update of a plan in mode EXA_FV_MUSCL_HANCOCK (its term sets see the state alone: no centres, no time)
-static int fv_muscl(exa_fv_plan* p, double* Q_dev, double dt, double h, const long* slot_dev, void* stream, double* out_dev) {
-    if (p->streamed)
-        return fv_muscl_stream_launch(p->P, p->H, p->n_real, p->n_aux, p->n_patches, p->pde, Q_dev, dt, h, slot_dev, (hipStream_t)stream, out_dev);
-    return fv_muscl_launch(p->dim, p->P, p->H, p->n_real, p->n_aux, p->n_patches, p->pde, Q_dev, dt, h, slot_dev, (hipStream_t)stream, out_dev);
+// one launch of the plan's update through the slot of its mode.  grid: the grid step (Q halo-less and only read, out the new states).  The term sets
+// of EXA_FV_MUSCL_HANCOCK see the state alone: its entry reads no centres and no time
+static int fv_step(const exa_fv_plan* p, double* Q, double* out, const long* slot, const double* centre, double t, double dt, double h, const FvGrid* grid,
+                   void* stream) {
+    const FvLaunch a{p->mode, grid ? FV_FORM_GRID : (p->streamed ? FV_FORM_STREAMED : FV_FORM_RESIDENT), p->dim, p->P, p->H, p->n_real, p->n_aux,
+                     p->n_patches, Q, out, slot, dt, h, centre, t, grid, (hipStream_t)stream};
+    const auto run = p->mode == EXA_FV_MUSCL_HANCOCK ? fv_muscl_slot(p->k, p->pde) : slot_or_error(p->k->fv, p->pde, "FV patch kernel");
+    return run ? run(a) : EXA_ERR_INVALID;
 }
 
 int exa_fv_time_step_device_masked(exa_fv_plan* p, double* Q_dev, const long* slot_dev, double dt, double h, void* stream) {
@@ -343,8 +287,7 @@ int exa_fv_time_step_device_masked(exa_fv_plan* p, double* Q_dev, const long* sl
     if (p->mode == EXA_FV_MUSCL_HANCOCK && !(h > 0.0)) { set_error("EXA_FV_MUSCL_HANCOCK needs the volume size h > 0"); return EXA_ERR_INVALID; }
     int rc = use_device(p->device);
     if (rc) return rc;
-    if (p->mode == EXA_FV_MUSCL_HANCOCK) return fv_muscl(p, Q_dev, dt, h, slot_dev, stream, nullptr);
-    return fv_launch(p->mode, p->dim, p->P, p->H, p->n_real, p->n_aux, p->n_patches, p->pde, Q_dev, dt, h, slot_dev, (hipStream_t)stream);
+    return fv_step(p, Q_dev, nullptr, slot_dev, nullptr, 0.0, dt, h, nullptr, stream);
 }
 
 int exa_fv_time_step_device_masked_at(exa_fv_plan* p, double* Q_dev, const long* slot_dev, const double* centre_dev, double t, double dt, double h,
@@ -353,9 +296,7 @@ int exa_fv_time_step_device_masked_at(exa_fv_plan* p, double* Q_dev, const long*
     if (!(h > 0.0)) { set_error("exa_fv_time_step_device_masked_at needs the volume size h > 0 (volume centres, dt / h)"); return EXA_ERR_INVALID; }
     int rc = use_device(p->device);
     if (rc) return rc;
-    if (p->mode == EXA_FV_MUSCL_HANCOCK) return fv_muscl(p, Q_dev, dt, h, slot_dev, stream, nullptr);
-    return fv_launch(p->mode, p->dim, p->P, p->H, p->n_real, p->n_aux, p->n_patches, p->pde, Q_dev, dt, h, slot_dev, (hipStream_t)stream, nullptr,
-                     centre_dev, t);
+    return fv_step(p, Q_dev, nullptr, slot_dev, centre_dev, t, dt, h, nullptr, stream);
 }
 
 int exa_fv_time_step_device_oop(exa_fv_plan* p, const double* QIn_dev, double* QOut_dev, const double* centre_dev, double t, double dt,
@@ -364,10 +305,8 @@ int exa_fv_time_step_device_oop(exa_fv_plan* p, const double* QIn_dev, double* Q
     if (!(h > 0.0)) { set_error("exa_fv_time_step_device_oop needs the volume size h > 0 (volume centres, dt / h)"); return EXA_ERR_INVALID; }
     int rc = use_device(p->device);
     if (rc) return rc;
-    if (p->mode == EXA_FV_MUSCL_HANCOCK) return fv_muscl(p, const_cast<double*>(QIn_dev), dt, h, nullptr, stream, QOut_dev);
-    // (the kernel only reads QIn: the const is cast away for the signature it shares with the in-place call)
-    return fv_launch(p->mode, p->dim, p->P, p->H, p->n_real, p->n_aux, p->n_patches, p->pde, const_cast<double*>(QIn_dev), dt, h, nullptr,
-                     (hipStream_t)stream, QOut_dev, centre_dev, t);
+    // (the kernel only reads QIn: the const is cast away for the argument it shares with the in-place call)
+    return fv_step(p, const_cast<double*>(QIn_dev), QOut_dev, nullptr, centre_dev, t, dt, h, nullptr, stream);
 }
 
 int exa_fv_time_step_device_at(exa_fv_plan* p, double* Q_dev, const double* centre_dev, double t, double dt, double h, void* stream) {
@@ -375,12 +314,46 @@ int exa_fv_time_step_device_at(exa_fv_plan* p, double* Q_dev, const double* cent
     if (!(h > 0.0)) { set_error("exa_fv_time_step_device_at needs the volume size h > 0 (volume centres, dt / h)"); return EXA_ERR_INVALID; }
     int rc = use_device(p->device);
     if (rc) return rc;
-    if (p->mode == EXA_FV_MUSCL_HANCOCK) return fv_muscl(p, Q_dev, dt, h, nullptr, stream, nullptr);
-    return fv_launch(p->mode, p->dim, p->P, p->H, p->n_real, p->n_aux, p->n_patches, p->pde, Q_dev, dt, h, nullptr, (hipStream_t)stream, nullptr,
-                     centre_dev, t);
+    return fv_step(p, Q_dev, nullptr, nullptr, centre_dev, t, dt, h, nullptr, stream);
 }
 
-// the grid step behind both entries; who: the entry that was called (error messages)
+// face_kind[2 dim] (null: every face periodic) of the entry `who` -> bkind; a face that is not periodic needs face_data_dev.  -> *bounded: there is one.
+// hints: the entry's messages end in the way out (the wording exa_fv_grid_step_muscl_device has had; the older entries keep theirs)
+static int check_face_kinds(const char* who, bool hints, int dim, const int* face_kind, const double* face_data_dev, int* bkind, bool* bounded) {
+    *bounded = false;
+    for (int f = 0; face_kind && f < 2 * dim; f++) {
+        if (face_kind[f] < EXA_FV_FACE_PERIODIC || face_kind[f] > EXA_FV_FACE_MIRROR) {
+            set_error("%s: face_kind[%d] = %d is none of EXA_FV_FACE_PERIODIC / _STATE / _MIRROR", who, f, face_kind[f]);
+            return EXA_ERR_INVALID;
+        }
+        bkind[f] = face_kind[f];
+        *bounded = *bounded || face_kind[f] != EXA_FV_FACE_PERIODIC;
+    }
+    if (*bounded && !face_data_dev) { set_error("%s: a face that is not periodic needs face_data_dev%s", who, hints ? " (its state or its signs)" : ""); return EXA_ERR_INVALID; }
+    return EXA_OK;
+}
+
+// what both grid steps ask of face_kind, face_data_dev and grid[] -> *ga; who: the entry that was called (error messages)
+static int fv_grid_args(const char* who, bool hints, const exa_fv_plan* p, const long* grid, const int* face_kind, const double* face_data_dev, double* lambda_next_dev,
+                        FvGrid* ga) {
+    *ga = FvGrid{{1, 1, 1}, {0, 0, 0, 0, 0, 0}, nullptr, lambda_next_dev};
+    bool bounded;
+    int rc = check_face_kinds(who, hints, p->dim, face_kind, face_data_dev, ga->bkind, &bounded);
+    if (rc) return rc;
+    ga->bstate = bounded ? face_data_dev : nullptr;                // (null: the kernels take every face as periodic)
+    long n = 1;
+    for (int a = 0; a < p->dim; a++) {
+        if (grid[a] < 1 || grid[a] > 0x7fffffffL) { set_error("%s: grid[%d] = %ld", who, a, grid[a]); return EXA_ERR_INVALID; }
+        ga->g[a] = (int)grid[a];
+        n *= grid[a];
+    }
+    if (n != p->n_patches) { set_error("%s: the grid has %ld patches, the plan %ld%s", who, n, p->n_patches, hints ? ": create the plan with n_patches = the product of grid" : ""); return EXA_ERR_INVALID; }
+    // (the kernels decode a patch's grid coordinates in 32-bit arithmetic: fv_grid_coords, fv_muscl_patch_coords)
+    if (n > 0xffffffffL) { set_error("%s: %ld patches -- a grid holds at most 2^32 - 1", who, n); return EXA_ERR_INVALID; }
+    return EXA_OK;
+}
+
+// the grid step behind both entries of the first-order modes; who: the entry that was called (error messages)
 static int fv_grid_step(const char* who, exa_fv_plan* p, const double* Q_dev, double* QNext_dev, const long* grid, const int* face_kind, const double* face_data_dev,
                         const double* centre_dev, double t, double dt, double h, double* lambda_next_dev, void* stream) {
     if (!p || !grid || ((!Q_dev || !QNext_dev) && p->count > 0)) { set_error("%s: NULL argument", who); return EXA_ERR_INVALID; }
@@ -391,32 +364,13 @@ static int fv_grid_step(const char* who, exa_fv_plan* p, const double* Q_dev, do
     }
     if (Q_dev == QNext_dev) { set_error("%s: the new states need an array of their own (the neighbours read the old ones)", who); return EXA_ERR_INVALID; }
     if (p->mode == EXA_FV_RUSANOV && !(h > 0.0)) { set_error("%s: EXA_FV_RUSANOV needs the volume size h > 0", who); return EXA_ERR_INVALID; }
-    FvGridArgs ga{QNext_dev, nullptr, {1, 1, 1}, lambda_next_dev, {0, 0, 0, 0, 0, 0}};
-    bool bounded = false;
-    for (int f = 0; face_kind && f < 2 * p->dim; f++) {
-        if (face_kind[f] < EXA_FV_FACE_PERIODIC || face_kind[f] > EXA_FV_FACE_MIRROR) {
-            set_error("%s: face_kind[%d] = %d is none of EXA_FV_FACE_PERIODIC / _STATE / _MIRROR", who, f, face_kind[f]);
-            return EXA_ERR_INVALID;
-        }
-        ga.bkind[f] = face_kind[f];
-        bounded = bounded || face_kind[f] != EXA_FV_FACE_PERIODIC;
-    }
-    if (bounded && !face_data_dev) { set_error("%s: a face that is not periodic needs face_data_dev", who); return EXA_ERR_INVALID; }
-    ga.bstate = bounded ? face_data_dev : nullptr;                 // (null: the kernels take every face as periodic)
-    long n = 1;
-    for (int a = 0; a < p->dim; a++) {
-        if (grid[a] < 1 || grid[a] > 0x7fffffffL) { set_error("%s: grid[%d] = %ld", who, a, grid[a]); return EXA_ERR_INVALID; }
-        ga.g[a] = (int)grid[a];
-        n *= grid[a];
-    }
-    if (n != p->n_patches) { set_error("%s: the grid has %ld patches, the plan %ld", who, n, p->n_patches); return EXA_ERR_INVALID; }
-    // (the kernels decode a patch's grid coordinates in 32-bit arithmetic: fv_grid_coords)
-    if (n > 0xffffffffL) { set_error("%s: %ld patches -- a grid holds at most 2^32 - 1", who, n); return EXA_ERR_INVALID; }
-    if (p->H > p->P) { set_error("%s: halo_size %d exceeds patch_size %d (the halo would reach past the face neighbour)", who, p->H, p->P); return EXA_ERR_INVALID; }
-    int rc = use_device(p->device);
+    FvGrid ga;
+    int rc = fv_grid_args(who, false, p, grid, face_kind, face_data_dev, lambda_next_dev, &ga);
     if (rc) return rc;
-    return fv_launch(p->mode, p->dim, p->P, p->H, p->n_real, p->n_aux, p->n_patches, p->pde, const_cast<double*>(Q_dev), dt, h, nullptr,
-                     (hipStream_t)stream, nullptr, centre_dev, t, &ga);
+    if (p->H > p->P) { set_error("%s: halo_size %d exceeds patch_size %d (the halo would reach past the face neighbour)", who, p->H, p->P); return EXA_ERR_INVALID; }
+    rc = use_device(p->device);
+    if (rc) return rc;
+    return fv_step(p, const_cast<double*>(Q_dev), QNext_dev, nullptr, centre_dev, t, dt, h, &ga, stream);
 }
 
 int exa_fv_grid_step_device_bc(exa_fv_plan* p, const double* Q_dev, double* QNext_dev, const long* grid, const int* face_kind, const double* face_data_dev,
@@ -453,29 +407,12 @@ int exa_fv_grid_step_muscl_device(exa_fv_plan* p, const double* Q_dev, double* Q
     }
     if (Q_dev == QNext_dev) { set_error("%s: the new states need an array of their own (the neighbours read the old ones): pass two arrays and swap them", who); return EXA_ERR_INVALID; }
     if (!(h > 0.0)) { set_error("%s: EXA_FV_MUSCL_HANCOCK needs the volume size h > 0", who); return EXA_ERR_INVALID; }
-    FvMusclGrid ga{{1, 1, 1}, {0, 0, 0, 0, 0, 0}, nullptr, lambda_next_dev};
-    bool bounded = false;
-    for (int f = 0; face_kind && f < 2 * p->dim; f++) {
-        if (face_kind[f] < EXA_FV_FACE_PERIODIC || face_kind[f] > EXA_FV_FACE_MIRROR) {
-            set_error("%s: face_kind[%d] = %d is none of EXA_FV_FACE_PERIODIC / _STATE / _MIRROR", who, f, face_kind[f]);
-            return EXA_ERR_INVALID;
-        }
-        ga.bkind[f] = face_kind[f];
-        bounded = bounded || face_kind[f] != EXA_FV_FACE_PERIODIC;
-    }
-    if (bounded && !face_data_dev) { set_error("%s: a face that is not periodic needs face_data_dev (its state or its signs)", who); return EXA_ERR_INVALID; }
-    ga.bstate = bounded ? face_data_dev : nullptr;                 // (null: the kernel takes every face as periodic)
-    long n = 1;
-    for (int a = 0; a < p->dim; a++) {
-        if (grid[a] < 1 || grid[a] > 0x7fffffffL) { set_error("%s: grid[%d] = %ld", who, a, grid[a]); return EXA_ERR_INVALID; }
-        ga.g[a] = (int)grid[a];
-        n *= grid[a];
-    }
-    if (n != p->n_patches) { set_error("%s: the grid has %ld patches, the plan %ld: create the plan with n_patches = the product of grid", who, n, p->n_patches); return EXA_ERR_INVALID; }
-    if (n > 0xffffffffL) { set_error("%s: %ld patches -- a grid holds at most 2^32 - 1", who, n); return EXA_ERR_INVALID; }
-    int rc = use_device(p->device);
+    FvGrid ga;
+    int rc = fv_grid_args(who, true, p, grid, face_kind, face_data_dev, lambda_next_dev, &ga);
     if (rc) return rc;
-    return fv_muscl_grid_launch(p->dim, p->P, p->n_real, p->n_aux, p->n_patches, p->pde, Q_dev, QNext_dev, dt, h, &ga, (hipStream_t)stream);
+    rc = use_device(p->device);
+    if (rc) return rc;
+    return fv_step(p, const_cast<double*>(Q_dev), QNext_dev, nullptr, nullptr, 0.0, dt, h, &ga, stream);
 }
 
 int exa_fv_max_eigenvalue(exa_fv_plan* p, const double* Q_dev, int halo_less, const double* centre_dev, double t, double h, double* lambda_dev,
@@ -484,8 +421,9 @@ int exa_fv_max_eigenvalue(exa_fv_plan* p, const double* Q_dev, int halo_less, co
     int rc = use_device(p->device);
     if (rc) return rc;
     // (a halo-less array is a patch array with halo_size 0: every volume is an interior volume)
-    return fv_maxeig_launch(p->dim, p->P, halo_less ? 0 : p->H, p->n_real, p->n_aux, p->n_patches, p->pde, Q_dev, lambda_dev, (hipStream_t)stream,
-                            centre_dev, t, h);
+    const auto scan = slot_or_error(p->k->fv_maxeig, p->pde, "FV eigenvalue scan");
+    return scan ? scan(p->dim, p->P, halo_less ? 0 : p->H, p->n_real + p->n_aux, p->n_patches, Q_dev, lambda_dev, centre_dev, t, h, (hipStream_t)stream)
+                : EXA_ERR_INVALID;
 }
 
 long exa_fv_qout_count(const exa_fv_plan* plan) {
@@ -525,7 +463,8 @@ int exa_dg_plan_create(int device, int dim, int N, int n_vars, int pde, int n_pi
     if (!plan || !ncells) { set_error("exa_dg_plan_create: NULL argument"); return EXA_ERR_INVALID; }
     *plan = nullptr;
     if (dim != 2 && dim != 3) { set_error("check viability of inputs"); return EXA_ERR_INVALID; }
-    const DgLaunchTable* tab = dg_launch_table(dim, pde);
+    const PdeKernels* k = pde_kernels(pde);
+    const DgLaunchTable* tab = k ? k->dg[dim] : nullptr;
     if (!tab) { set_error("ADER-DG: no kernels for dim %d, pde %d", dim, pde); return EXA_ERR_INVALID; }
     if (N < 2 || N > tab->max_n) {
         set_error("ADER-DG: N = %d unsupported for dim %d (2..%d)", N, dim, tab->max_n);
@@ -545,6 +484,7 @@ int exa_dg_plan_create(int device, int dim, int N, int n_vars, int pde, int n_pi
     p->n_it = n_picard < 0 ? N : n_picard;
     p->nc[0] = ncells[0]; p->nc[1] = ncells[1]; p->nc[2] = dim == 3 ? ncells[2] : 1;
     p->ncells = nc;
+    p->k = k;
     p->tab = tab;
     if (build_dg_operators(N, &p->ops) != 0) { delete p; set_error("operator construction failed for N = %d", N); return EXA_ERR_INVALID; }
     // operator block image in HBM
@@ -885,18 +825,11 @@ long exa_lim_patch_count_halo(const exa_dg_plan* p, int halo) {
 int exa_lim_project_patches_halo2(exa_dg_plan* p, const double* u_dev, const long* cells_dev, long n, double* patch_dev, const int* face_kind,
                                   const double* face_data_dev, void* stream) {
     if (!p || !u_dev || (n > 0 && (!cells_dev || !patch_dev)) || n < 0) { set_error("exa_lim_project_patches_halo2: bad argument"); return EXA_ERR_INVALID; }
-    if (face_kind)
-        for (int f = 0; f < 2 * p->dim; f++) {
-            if (face_kind[f] < EXA_FV_FACE_PERIODIC || face_kind[f] > EXA_FV_FACE_MIRROR) {
-                set_error("exa_lim_project_patches_halo2: face_kind[%d] = %d is not EXA_FV_FACE_PERIODIC, _STATE or _MIRROR", f, face_kind[f]);
-                return EXA_ERR_INVALID;
-            }
-            if (face_kind[f] != EXA_FV_FACE_PERIODIC && !face_data_dev) {
-                set_error("exa_lim_project_patches_halo2: face %d is not periodic and face_data_dev is NULL", f);
-                return EXA_ERR_INVALID;
-            }
-        }
-    int rc = use_device(p->device);
+    int bkind[6];
+    bool bounded;
+    int rc = check_face_kinds("exa_lim_project_patches_halo2", false, p->dim, face_kind, face_data_dev, bkind, &bounded);
+    if (rc) return rc;
+    rc = use_device(p->device);
     if (rc) return rc;
     rc = lim_tables(p);
     if (rc) return rc;
@@ -916,25 +849,17 @@ int exa_lim_reconstruct_patches_halo(exa_dg_plan* p, const double* patch_dev, co
                                (hipStream_t)stream);
 }
 
-// the registered term set of the plan if it carries its own criterion (EXA_PDE_FLAG_ADMISSIBLE), else null
-static const UserPde* lim_user(const exa_dg_plan* p) {
-    if (p->pde < 100 || p->pde - 100 >= (int)g_user.size()) return nullptr;
-    const UserPde* u = &g_user[p->pde - 100];
-    return (u->flags & EXA_PDE_FLAG_ADMISSIBLE) ? u : nullptr;
-}
-
-long exa_lim_bounds_count(const exa_dg_plan* p) {
-    if (!p) return 0;
-    const UserPde* up = lim_user(p);
-    return up ? 2L * up->k_dmp : 4;
-}
+// (a term set without a detector unit of its own -- null slots -- is watched by the Euler-layout criterion of limiter.hip: k_dmp = 2.  So is the
+// zero-filled stand-in for a plan that the tests of the argument checks hand in on a machine without a GPU, which has no table: this is the only
+// read of p->k in front of a use_device, where those tests end)
+long exa_lim_bounds_count(const exa_dg_plan* p) { return p ? 2L * (p->k ? p->k->k_dmp : 2) : 0; }
 
 int exa_lim_snapshot(exa_dg_plan* p, const double* u_dev, double* u_old_dev, double* bounds_dev, void* stream) {
     const bool no_bounds = p && u_dev && exa_lim_bounds_count(p) == 0;         // (nothing watched: bounds_dev is not touched)
     if (!p || !u_dev || (!bounds_dev && !no_bounds) || u_dev == u_old_dev) { set_error("exa_lim_snapshot: bad argument (plan, u_dev or bounds_dev is NULL, or u_old_dev == u_dev)"); return EXA_ERR_INVALID; }
     int rc = use_device(p->device);
     if (rc) return rc;
-    if (const UserPde* up = lim_user(p)) return up->lim_snap(p->dim, p->N, p->ncells, u_dev, u_old_dev, bounds_dev, stream);
+    if (const auto own = p->k->lim_snapshot) return own(p->dim, p->N, p->ncells, u_dev, u_old_dev, bounds_dev, (hipStream_t)stream);
     return limiter_snapshot(p->dim, p->N, p->nv, p->ncells, u_dev, u_old_dev, bounds_dev, (hipStream_t)stream);
 }
 
@@ -944,8 +869,8 @@ int exa_lim_detect(exa_dg_plan* p, const double* u_cand_dev, const double* bound
     if (!p || !u_cand_dev || (!bounds_dev && !no_bounds) || !mask_dev) { set_error("exa_lim_detect: NULL argument"); return EXA_ERR_INVALID; }
     int rc = use_device(p->device);
     if (rc) return rc;
-    const UserPde* up = lim_user(p);
-    if (!up && p->nv < 2) { set_error("exa_lim_detect: needs a density and an energy (n_vars >= 2), the plan has %d", p->nv); return EXA_ERR_INVALID; }
+    const auto own = p->k->lim_detect;
+    if (!own && p->nv < 2) { set_error("exa_lim_detect: needs a density and an energy (n_vars >= 2), the plan has %d", p->nv); return EXA_ERR_INVALID; }
     if (!(d0 >= 0.0) || !(eps >= 0.0) || floor != floor) { set_error("exa_lim_detect: d0 and eps must be >= 0 and floor a number"); return EXA_ERR_INVALID; }
     LimGhosts gb{};
     for (int f = 0; f < 2 * p->dim; f++) {
@@ -957,31 +882,26 @@ int exa_lim_detect(exa_dg_plan* p, const double* u_cand_dev, const double* bound
             gb.layer[f] = ghost_bounds_dev[f];
         }
     }
-    if (up) return up->lim_det(p->dim, p->N, p->nc, u_cand_dev, bounds_dev, gb.layer, face_kind, d0, eps, floor, mask_dev, stream);
+    if (own) return own(p->dim, p->N, p->nc, u_cand_dev, bounds_dev, &gb, face_kind, d0, eps, floor, mask_dev, (hipStream_t)stream);
     return limiter_detect(p->dim, p->N, p->nv, p->nc, u_cand_dev, bounds_dev, &gb, face_kind, d0, eps, floor, mask_dev, (hipStream_t)stream);
 }
 
-// term sets the conservative interface is built for: the built-in Euler (5 variables) and advection (1 variable) sets, and registered sets that
-// ask for it (EXA_PDE_FLAG_CONSERVATIVE) -- *user then points to the registered one
-static int lim_conservative_pde(const exa_dg_plan* p, const char* who, const UserPde** user) {
-    *user = nullptr;
-    if (exa_pde_flags(p->pde) & (EXA_PDE_FLAG_XT | EXA_PDE_FLAG_NCP)) {
+// The slots of the conservative interface: the built-in Euler (5 variables) and advection (1 variable) sets have them, and registered sets that
+// ask for the interface (EXA_PDE_FLAG_CONSERVATIVE: exa_register_pde has seen their unit).  -> the plan's table, or null with the message
+static const PdeKernels* lim_conservative(const exa_dg_plan* p, const char* who) {
+    const PdeKernels* k = p->k;
+    if (k->flags & (EXA_PDE_FLAG_XT | EXA_PDE_FLAG_NCP)) {
         set_error("%s: term set %d carries position- / time-dependent terms or a non-conservative product; the conservative interface is built for "
                   "term sets of the state alone without one", who, p->pde);
-        return EXA_ERR_INVALID;
+        return nullptr;
     }
-    if (exa_pde_flags(p->pde) & EXA_PDE_FLAG_CONSERVATIVE) {
-        const UserPde* u = &g_user[p->pde - 100];
-        if (p->nv != u->nv) { set_error("%s: term set %d has %d variables, the plan %d", who, p->pde, u->nv, p->nv); return EXA_ERR_INVALID; }
-        *user = u;
-        return EXA_OK;
-    }
-    if (!((p->pde == 1 && p->nv == 5) || (p->pde == 2 && p->nv == 1))) {
+    if ((k->flags & EXA_PDE_FLAG_CONSERVATIVE) && p->nv != k->nv) { set_error("%s: term set %d has %d variables, the plan %d", who, p->pde, k->nv, p->nv); return nullptr; }
+    if (!k->lim_face_flux || !k->lim_interface_correct || p->nv != k->nv) {
         set_error("%s: term set %d with %d variables; the conservative interface is built for the built-in Euler (pde 1, 5 variables) and advection (pde 2, 1 variable) sets "
                   "and for registered sets generated with SympyPDE(conservative_interface=True)", who, p->pde, p->nv);
-        return EXA_ERR_INVALID;
+        return nullptr;
     }
-    return EXA_OK;
+    return k;
 }
 
 long exa_lim_face_flux_count(const exa_dg_plan* p) { return p ? 2L * p->dim * p->nv * lpow(p->N, p->dim - 1) : 0; }
@@ -990,14 +910,12 @@ int exa_lim_face_flux(exa_dg_plan* p, const double* patch_dev, const long* cells
     if (!p || n < 0 || (n > 0 && (!patch_dev || !cells_dev || !fvflux_dev))) { set_error("exa_lim_face_flux: bad argument (NULL plan or array, or n < 0)"); return EXA_ERR_INVALID; }
     int rc = use_device(p->device);
     if (rc) return rc;
-    const UserPde* up;
-    rc = lim_conservative_pde(p, "exa_lim_face_flux", &up);
-    if (rc) return rc;
+    const PdeKernels* k = lim_conservative(p, "exa_lim_face_flux");
+    if (!k) return EXA_ERR_INVALID;
     rc = lim_tables(p);
     if (rc) return rc;
     const double* Rdev = static_cast<const double*>(p->ops.lim) + (size_t)p->N * (2 * p->N - 1);
-    if (up) return up->lim_flux(p->dim, p->N, patch_dev, cells_dev, n, fvflux_dev, Rdev, stream) == 0 ? EXA_OK : EXA_ERR_HIP;
-    return limiter_face_flux(p->dim, p->N, p->pde, patch_dev, cells_dev, n, fvflux_dev, Rdev, (hipStream_t)stream) == 0 ? EXA_OK : EXA_ERR_HIP;
+    return k->lim_face_flux(p->dim, p->N, patch_dev, cells_dev, n, fvflux_dev, Rdev, (hipStream_t)stream) == 0 ? EXA_OK : EXA_ERR_HIP;
 }
 
 int exa_lim_interface_correct(exa_dg_plan* p, double* u_dev, const double* trace_dev, const long* cells_dev, long n, const unsigned char* mask_dev,
@@ -1008,9 +926,8 @@ int exa_lim_interface_correct(exa_dg_plan* p, double* u_dev, const double* trace
     }
     int rc = use_device(p->device);
     if (rc) return rc;
-    const UserPde* up;
-    rc = lim_conservative_pde(p, "exa_lim_interface_correct", &up);
-    if (rc) return rc;
+    const PdeKernels* k = lim_conservative(p, "exa_lim_interface_correct");
+    if (!k) return EXA_ERR_INVALID;
     for (int f = 0; f < 2 * p->dim; f++) {
         const int kind = face_kind ? face_kind[f] : EXA_LIM_FACE_PERIODIC;
         if (kind == EXA_LIM_FACE_GHOST) {
@@ -1021,11 +938,8 @@ int exa_lim_interface_correct(exa_dg_plan* p, double* u_dev, const double* trace
     }
     for (int a = 0; a < p->dim; a++)
         if (!(dx[a] > 0.0)) { set_error("exa_lim_interface_correct: dx[%d] must be positive", a); return EXA_ERR_INVALID; }
-    if (up)
-        return up->lim_corr(p->dim, p->N, p->nc, u_dev, trace_dev, cells_dev, n, mask_dev, face_kind, fvflux_dev, dt, dx, p->ops.w, p->ops.phiL, p->ops.phiR,
-                            stream) == 0 ? EXA_OK : EXA_ERR_HIP;
-    return limiter_interface_correct(p->dim, p->N, p->pde, p->nc, u_dev, trace_dev, cells_dev, n, mask_dev, face_kind, fvflux_dev, dt, dx,
-                                     p->ops.w, p->ops.phiL, p->ops.phiR, (hipStream_t)stream) == 0 ? EXA_OK : EXA_ERR_HIP;
+    return k->lim_interface_correct(p->dim, p->N, p->nc, u_dev, trace_dev, cells_dev, n, mask_dev, face_kind, fvflux_dev, dt, dx, p->ops.w, p->ops.phiL,
+                                    p->ops.phiR, (hipStream_t)stream) == 0 ? EXA_OK : EXA_ERR_HIP;
 }
 
 int exa_dg_max_eigenvalue(exa_dg_plan* p, const double* u_dev, double* lambda_dev, void* stream) {

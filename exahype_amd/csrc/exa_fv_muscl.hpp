@@ -331,36 +331,6 @@ fv_muscl_kernel(double* __restrict__ Q, double* __restrict__ out, const long* __
     fv_muscl_correct<DIM, PDE, NT, false>(img, del, Q, out, slot, first, np, P, H, m, V, r, dt);
 }
 
-// launch for one (DIM, PDE); the plan (patches per workgroup, LDS bytes) is fv_muscl_plan's, which exa_fv_plan_create has checked
-template <int DIM, class PDE>
-int fv_muscl_run(int P, int H, int m, int V, long n_patches, double* Q, double dt, double h, const long* slot, hipStream_t s, double* out) {
-    FvMusclPlan pl;
-    if (!fv_muscl_plan(DIM, P, m, V, &pl)) {
-        set_error("MUSCL-Hancock: the patch needs %zu B of LDS, %zu B are available", pl.lds, FV_MUSCL_LDS_AVAILABLE);
-        return -1;
-    }
-    if (H < 2) { set_error("MUSCL-Hancock reads two halo layers"); return -1; }
-    if (m > FVM_MAXV) { set_error("n_real = %d exceeds %d", m, FVM_MAXV); return -1; }
-    if (n_patches <= 0) return 0;
-    const long nblk = (n_patches + pl.ppb - 1) / pl.ppb;
-    if (nblk > 0x7fffffffL) { set_error("MUSCL-Hancock: %ld patches are more than one launch covers", n_patches); return -1; }
-    const double r = dt / h;
-    auto go = [&](auto kern, int nt) -> int {
-        if (pl.lds > 64 * 1024) {
-            hipError_t ea = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)pl.lds);
-            if (ea != hipSuccess) { set_error("hipFuncSetAttribute(fv muscl, %zu B LDS): %s", pl.lds, hipGetErrorString(ea)); return -2; }
-        }
-        hipLaunchKernelGGL(kern, dim3((unsigned)nblk), dim3(nt), pl.lds, s, Q, out, slot, P, H, m, V, r, n_patches, pl.ppb, dt);
-        hipError_t e = hipGetLastError();
-        if (e != hipSuccess) { set_error("fv_muscl launch: %s", hipGetErrorString(e)); return -2; }
-        return 0;
-    };
-    if constexpr (DIM == 2) {                                     // (fv_muscl_plan asks for 512 threads in 2-D only)
-        if (pl.nt == 512) return go(fv_muscl_kernel<DIM, PDE, 512>, 512);
-    }
-    return go(fv_muscl_kernel<DIM, PDE, 256>, 256);
-}
-
 // ---- the PLANE-STREAMING form (3-D; a plan of exa_fv_plan_create_streamed): for patches whose whole window does not fit a compute unit's LDS.  One
 // workgroup per patch walks the planes of axis 0 once and keeps a ring of `ring` window planes [T][T][V] and three predictor planes [D][D][m]:
 //   step s = 0 .. T - 1:   stage window plane s                     (H = 2: one contiguous block of the patch, 16-byte loads; else row by row)
@@ -476,31 +446,6 @@ fv_muscl_stream_kernel(double* __restrict__ Q, double* __restrict__ out, const l
     }
 }
 
-// launch of the streamed form for one PDE; the plan is fv_muscl_stream_plan's, which exa_fv_plan_create_streamed has checked
-template <class PDE>
-int fv_muscl_stream_run(int P, int H, int m, int V, long n_patches, double* Q, double dt, double h, const long* slot, hipStream_t s, double* out) {
-    FvMusclPlan pl;
-    if (P < 1 || P > 1024 || !fv_muscl_stream_plan(P, m, V, &pl)) {
-        set_error("MUSCL-Hancock (streamed): five window planes and three predictor planes need %zu B of LDS, %zu B are available",
-                  P >= 1 && P <= 1024 ? pl.lds : (size_t)-1, FV_MUSCL_LDS_AVAILABLE);
-        return -1;
-    }
-    if (H < 2) { set_error("MUSCL-Hancock reads two halo layers"); return -1; }
-    if (m > FVM_MAXV) { set_error("n_real = %d exceeds %d", m, FVM_MAXV); return -1; }
-    if (n_patches <= 0) return 0;
-    if (n_patches > 0x7fffffffL) { set_error("MUSCL-Hancock: %ld patches are more than one launch covers", n_patches); return -1; }
-    const double r = dt / h;
-    auto kern = fv_muscl_stream_kernel<PDE, 256>;
-    if (pl.lds > 64 * 1024) {
-        hipError_t ea = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)pl.lds);
-        if (ea != hipSuccess) { set_error("hipFuncSetAttribute(fv muscl stream, %zu B LDS): %s", pl.lds, hipGetErrorString(ea)); return -2; }
-    }
-    hipLaunchKernelGGL(kern, dim3((unsigned)n_patches), dim3(pl.nt), pl.lds, s, Q, out, slot, P, H, m, V, r, pl.ring, dt);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) { set_error("fv_muscl stream launch: %s", hipGetErrorString(e)); return -2; }
-    return 0;
-}
-
 // ---- the GRID step (exa_fv_grid_step_muscl_device): the patches are the cells of a Cartesian grid g[0] x g[1] (x g[2]), patch index row-major,
 // Q and out are HALO-LESS [patch][P^DIM][V] (P >= 2), Q is only read.  Only the staging differs from fv_muscl_kernel: the window of a patch is
 // gathered from the patch, its face neighbours AND its diagonal neighbours (the edge entries), every outside axis resolved on its own --
@@ -514,7 +459,7 @@ int fv_muscl_stream_run(int P, int H, int m, int V, long n_patches, double* Q, d
 // Neighbours live in other workgroups, which is why the new states go to a second array.
 
 // grid coordinates of a patch (32-bit arithmetic; the launcher has checked n_patches < 2^32)
-template <int DIM> __device__ __forceinline__ void fv_muscl_patch_coords(const FvMusclGrid& ga, long patch, int (&pg)[3]) {
+template <int DIM> __device__ __forceinline__ void fv_muscl_patch_coords(const FvGrid& ga, long patch, int (&pg)[3]) {
     unsigned x = (unsigned)patch;
     if constexpr (DIM == 3) { pg[2] = (int)(x % (unsigned)ga.g[2]); x /= (unsigned)ga.g[2]; } else pg[2] = 0;
     pg[1] = (int)(x % (unsigned)ga.g[1]);
@@ -524,7 +469,7 @@ template <int DIM> __device__ __forceinline__ void fv_muscl_patch_coords(const F
 // where the window entry at interior coordinates c (each in -2 .. P + 1) of the patch at pg finds its V doubles; mirrors: bit (axis * 2 + side) set
 // for every mirror face whose signs multiply them.  fbits: two bits per face, 0 where every face is periodic
 template <int DIM>
-__device__ __forceinline__ const double* fv_muscl_grid_source(const double* __restrict__ Q, const FvMusclGrid& ga, unsigned fbits, const int (&pg)[3],
+__device__ __forceinline__ const double* fv_muscl_grid_source(const double* __restrict__ Q, const FvGrid& ga, unsigned fbits, const int (&pg)[3],
                                                               const int (&c)[3], int P, int V, unsigned& mirrors) {
     int pn[3] = {pg[0], pg[1], pg[2]}, cn[3] = {c[0], c[1], c[2]};
     mirrors = 0u;
@@ -566,7 +511,7 @@ __device__ __forceinline__ void fv_muscl_lam_commit(double* lam, double mx) {
 
 template <int DIM, class PDE, int NT>
 __global__ void __launch_bounds__(NT)
-fv_muscl_grid_kernel(const double* __restrict__ Q, double* __restrict__ out, int P, int m, int V, double r, long n_patches, int ppb, FvMusclGrid ga,
+fv_muscl_grid_kernel(const double* __restrict__ Q, double* __restrict__ out, int P, int m, int V, double r, long n_patches, int ppb, FvGrid ga,
                      double dt) {
     extern __shared__ __attribute__((aligned(16))) double fvm_lds[];
     const int T = P + 4;
@@ -617,40 +562,73 @@ fv_muscl_grid_kernel(const double* __restrict__ Q, double* __restrict__ out, int
     if (ga.lam) fv_muscl_lam_commit(ga.lam, lmax);
 }
 
-// launch of the grid step for one (DIM, PDE): the plan is fv_muscl_plan's, unchanged
-template <int DIM, class PDE>
-int fv_muscl_grid_run(int P, int m, int V, long n_patches, const double* Q, double* out, double dt, double h, const FvMusclGrid& ga, hipStream_t s) {
+// ---- host side: the one entry of this update (PdeKernels::fv_muscl) for a term set.  It selects the form (a.form: FV_FORM_*) and the dimension; the
+// plan (patches per workgroup, threads, LDS bytes, ring) is fv_muscl_plan's / fv_muscl_stream_plan's, which exa_fv_plan_create[_streamed] has
+// checked.  The term sets of this mode see the state alone: a.centre and a.t are not read.
+template <class PDE>
+int fv_muscl_entry(const FvLaunch& a) {
+    const int P = a.P, m = a.n_real, V = a.n_real + a.n_aux;
+    const bool streamed = a.form == FV_FORM_STREAMED, grid = a.form == FV_FORM_GRID;
     FvMusclPlan pl;
-    if (!fv_muscl_plan(DIM, P, m, V, &pl)) {
+    if (streamed) {
+        if (P < 1 || P > 1024 || !fv_muscl_stream_plan(P, m, V, &pl)) {
+            set_error("MUSCL-Hancock (streamed): five window planes and three predictor planes need %zu B of LDS, %zu B are available",
+                      P >= 1 && P <= 1024 ? pl.lds : (size_t)-1, FV_MUSCL_LDS_AVAILABLE);
+            return -1;
+        }
+    } else if (!fv_muscl_plan(a.dim, P, m, V, &pl)) {
         set_error("MUSCL-Hancock: the patch needs %zu B of LDS, %zu B are available", pl.lds, FV_MUSCL_LDS_AVAILABLE);
         return -1;
     }
-    if (P < 2) { set_error("MUSCL-Hancock grid step: patch_size must be >= 2"); return -1; }
+    if (grid && P < 2) { set_error("MUSCL-Hancock grid step: patch_size must be >= 2"); return -1; }
+    if (!grid && a.H < 2) { set_error("MUSCL-Hancock reads two halo layers"); return -1; }
     if (m > FVM_MAXV) { set_error("n_real = %d exceeds %d", m, FVM_MAXV); return -1; }
-    if (!Q || !out || Q == out) { set_error("MUSCL-Hancock grid step: the new states need an array of their own"); return -1; }
-    if (n_patches > 0xffffffffL) { set_error("MUSCL-Hancock grid step: %ld patches -- a grid holds at most 2^32 - 1", n_patches); return -1; }
-    if (ga.lam) {
-        hipError_t e0 = hipMemsetAsync(ga.lam, 0, sizeof(double), s);
-        if (e0 != hipSuccess) { set_error("memset: %s", hipGetErrorString(e0)); return -2; }
+    if (grid) {
+        if (!a.grid) { set_error("MUSCL-Hancock grid step: no grid"); return -1; }
+        if (!a.Q || !a.out || a.Q == a.out) { set_error("MUSCL-Hancock grid step: the new states need an array of their own"); return -1; }
+        if (a.n_patches > 0xffffffffL) { set_error("MUSCL-Hancock grid step: %ld patches -- a grid holds at most 2^32 - 1", a.n_patches); return -1; }
+        if (a.grid->lam) {
+            hipError_t e0 = hipMemsetAsync(a.grid->lam, 0, sizeof(double), a.stream);
+            if (e0 != hipSuccess) { set_error("memset: %s", hipGetErrorString(e0)); return -2; }
+        }
     }
-    if (n_patches <= 0) return 0;
-    const long nblk = (n_patches + pl.ppb - 1) / pl.ppb;
-    if (nblk > 0x7fffffffL) { set_error("MUSCL-Hancock: %ld patches are more than one launch covers", n_patches); return -1; }
-    const double r = dt / h;
-    auto go = [&](auto kern, int nt) -> int {
+    if (a.n_patches <= 0) return 0;
+    const long nblk = (a.n_patches + pl.ppb - 1) / pl.ppb;
+    if (nblk > 0x7fffffffL) { set_error("MUSCL-Hancock: %ld patches are more than one launch covers", a.n_patches); return -1; }
+    const double r = a.dt / a.h;
+    // form: "", " stream", " grid" (error messages); args: the kernel's
+    auto launch = [&](const char* form, auto kern, int nt, auto... args) -> int {
         if (pl.lds > 64 * 1024) {
             hipError_t ea = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)pl.lds);
-            if (ea != hipSuccess) { set_error("hipFuncSetAttribute(fv muscl grid, %zu B LDS): %s", pl.lds, hipGetErrorString(ea)); return -2; }
+            if (ea != hipSuccess) { set_error("hipFuncSetAttribute(fv muscl%s, %zu B LDS): %s", form, pl.lds, hipGetErrorString(ea)); return -2; }
         }
-        hipLaunchKernelGGL(kern, dim3((unsigned)nblk), dim3(nt), pl.lds, s, Q, out, P, m, V, r, n_patches, pl.ppb, ga, dt);
+        hipLaunchKernelGGL(kern, dim3((unsigned)nblk), dim3(nt), pl.lds, a.stream, args...);
         hipError_t e = hipGetLastError();
-        if (e != hipSuccess) { set_error("fv_muscl grid launch: %s", hipGetErrorString(e)); return -2; }
+        if (e != hipSuccess) { set_error("fv_muscl%s launch: %s", form, hipGetErrorString(e)); return -2; }
         return 0;
     };
-    if constexpr (DIM == 2) {
-        if (pl.nt == 512) return go(fv_muscl_grid_kernel<DIM, PDE, 512>, 512);
+    auto in_dim = [&](auto dim_c) -> int {
+        constexpr int DIM = decltype(dim_c)::value;
+        if (streamed) {
+            if constexpr (DIM == 3) return launch(" stream", fv_muscl_stream_kernel<PDE, 256>, pl.nt, a.Q, a.out, a.slot, P, a.H, m, V, r, pl.ring, a.dt);
+            set_error("MUSCL-Hancock (streamed): the plane-streaming kernel is 3-D only");
+            return -1;
+        }
+        const double* Qin = a.Q;                                  // (the grid kernel only reads Q)
+        if constexpr (DIM == 2) {                                 // (fv_muscl_plan asks for 512 threads in 2-D only)
+            if (pl.nt == 512)
+                return grid ? launch(" grid", fv_muscl_grid_kernel<DIM, PDE, 512>, 512, Qin, a.out, P, m, V, r, a.n_patches, pl.ppb, *a.grid, a.dt)
+                            : launch("", fv_muscl_kernel<DIM, PDE, 512>, 512, a.Q, a.out, a.slot, P, a.H, m, V, r, a.n_patches, pl.ppb, a.dt);
+        }
+        return grid ? launch(" grid", fv_muscl_grid_kernel<DIM, PDE, 256>, 256, Qin, a.out, P, m, V, r, a.n_patches, pl.ppb, *a.grid, a.dt)
+                    : launch("", fv_muscl_kernel<DIM, PDE, 256>, 256, a.Q, a.out, a.slot, P, a.H, m, V, r, a.n_patches, pl.ppb, a.dt);
+    };
+    if (a.dim == 2) return in_dim(std::integral_constant<int, 2>{});
+    if constexpr (PDE::MAXDIM >= 3) {
+        if (a.dim == 3) return in_dim(std::integral_constant<int, 3>{});
     }
-    return go(fv_muscl_grid_kernel<DIM, PDE, 256>, 256);
+    set_error("MUSCL-Hancock: the term set has no kernel for dim %d", a.dim);
+    return -1;
 }
 
 }  // namespace exa

@@ -39,12 +39,6 @@ int limiter_project_halo2(int dim, int N, int nv, const long* nc, const double* 
 int limiter_snapshot(int dim, int N, int nv, long ncells, const double* u, double* u_old, double* bounds, hipStream_t s);
 int limiter_detect(int dim, int N, int nv, const long* nc, const double* u, const double* bounds, const LimGhosts* ghosts, const int* kinds,
                    double d0, double eps, double floor, unsigned char* mask, hipStream_t s);
-// conservative DG / FV interface (pde: 1 Euler, 2 advection): FV face fluxes of the listed patches at the DG face nodes, fvflux[slot][d*2+side][var][node];
-// their lift into the untroubled (mask == 0) face neighbours of the listed cells, one launch per (axis, side)
-int limiter_face_flux(int dim, int N, int pde, const double* patch, const long* cells, long n, double* fvflux, const double* Rdev, hipStream_t s);
-int limiter_interface_correct(int dim, int N, int pde, const long* nc, double* u, const double* trace, const long* cells, long n,
-                              const unsigned char* mask, const int* kinds, const double* fvflux, double dt, const double* dx,
-                              const double* w, const double* phiL, const double* phiR, hipStream_t s);
 
 struct StageBBox {
     long nc[3], lo[3], nb[3];
@@ -80,37 +74,75 @@ struct DgLaunchTable {
 // returns nullptr when (dim, pde) is not built
 const DgLaunchTable* dg_launch_table(int dim, int pde);
 
-// fv_rusanov.hip
+// One FV launch, for the built-in and the generated term sets alike (PdeKernels::fv, ::fv_muscl).
 // slot: nullptr, or one entry per patch (< 0: patch not in use, left untouched)
 // out != nullptr: out of place (QOut halo-less, [patch][P^dim][n_real + n_aux]); centre: [patch][dim] cell centres or nullptr; t: time
-// grid != nullptr: the GRID step -- the patches are the cells of a Cartesian grid g[0] x g[1] (x g[2]) (row-major), halo states are taken from the
-// face neighbours' interiors (periodic wrap), results go to grid->out (layout of Q).  bstate == null: every domain face is periodic; else the face
-// (axis, side) is of kind bkind[axis * 2 + side] with its V doubles of data in bstate[(axis * 2 + side) * V ..]: EXA_FV_FACE_PERIODIC (data unused),
-// _STATE (the prescribed state beyond the face) or _MIRROR (the patch's own interior layers reflected at the face, every variable times its sign)
+// grid != nullptr: the GRID step -- the patches are the cells of a Cartesian grid g[0] x g[1] (x g[2]) (row-major), Q and out are halo-less, halo
+// states are taken from the neighbours' interiors (periodic wrap), results go to out (layout of Q).  bstate == null: every domain face is periodic;
+// else the face (axis, side) is of kind bkind[axis * 2 + side] with its V doubles of data in bstate[(axis * 2 + side) * V ..]: EXA_FV_FACE_PERIODIC
+// (data unused), _STATE (the prescribed state beyond the face) or _MIRROR (the patch's own interior layers reflected at the face, every variable
+// times its sign); lam (optional): receives the largest eigenvalue of the NEW interior states (zeroed by the launcher on the stream)
 constexpr int FV_FACE_PERIODIC = 0, FV_FACE_STATE = 1, FV_FACE_MIRROR = 2;
-struct FvGridArgs {
-    double* out;
-    const double* bstate;
+struct FvGrid {            // (an argument of fv_muscl_grid_kernel: the layout stays)
     int g[3];
-    double* lam;          // optional: receives the largest eigenvalue of the NEW interior states (zeroed by fv_launch on the stream)
     int bkind[6];
+    const double* bstate;
+    double* lam;
 };
-int fv_launch(int mode, int dim, int P, int H, int n_real, int n_aux, long n_patches, int pde, double* Q, double dt,
-              double h, const long* slot, hipStream_t s, double* out = nullptr, const double* centre = nullptr, double t = 0.0,
-              const FvGridArgs* grid = nullptr);
-// max over the INTERIOR volumes of all patches and the directions of the largest eigenvalue -> lam[0] (device); centre / t / h as above
-int fv_maxeig_launch(int dim, int P, int H, int n_real, int n_aux, long n_patches, int pde, const double* Q, double* lam, hipStream_t s,
-                     const double* centre, double t, double h);
-// X: [n][3] positions (term sets that depend on position / time) or null; t: time
-int pde_eval_launch(int pde, int normal, long n, int stride, const double* Q, double* F, double* lam, hipStream_t s, const double* X = nullptr,
-                    double t = 0.0);
+// forms of the MUSCL-Hancock update: the whole window resident in LDS, the 3-D window walked plane by plane (a plan of
+// exa_fv_plan_create_streamed that is_streamed), the grid step on halo-less arrays (exa_fv_grid_step_muscl_device)
+constexpr int FV_FORM_RESIDENT = 0, FV_FORM_STREAMED = 1, FV_FORM_GRID = 2;
+struct FvLaunch {
+    int mode, form;        // EXA_FV_*; FV_FORM_* (EXA_FV_MUSCL_HANCOCK only)
+    int dim, P, H, n_real, n_aux;
+    long n_patches;
+    double* Q;             // (only read where out is given)
+    double* out;
+    const long* slot;
+    double dt, h;
+    const double* centre;
+    double t;
+    const FvGrid* grid;
+    hipStream_t stream;
+};
 
-// user PDE term sets registered at run time (capi.cpp: exa_register_pde), pde ids >= 100
-int user_fv_launch(int pde, int mode, int dim, int P, int H, int n_real, int n_aux, long n_patches, double* Q, double dt,
-                   double h, const long* slot, hipStream_t s, double* out, const double* centre, double t, const FvGridArgs* grid);
-int user_fv_maxeig(int pde, int dim, int P, int H, int n_real, int n_aux, long n_patches, const double* Q, double* lam, hipStream_t s,
-                   const double* centre, double t, double h);
-int user_pde_eval(int pde, int normal, long n, int stride, const double* Q, double* F, double* lam, hipStream_t s, const double* X, double t);
+// Everything a term set brings, built-in (ids 0 .. 2) or generated (ids >= 100, exa_register_pde): a slot is null where the set has no such unit.
+// pde_kernels() is the one lookup; the plans hold the pointer.  A side library fills its table through one extern "C" filler per unit it was built
+// with (the list `fillers` in exa_register_pde); a filler leaves a table of another PDE_KERNELS_ABI alone and returns non-zero.
+constexpr int PDE_KERNELS_ABI = 1;
+struct PdeKernels {
+    int abi;               // PDE_KERNELS_ABI of whoever filled the table
+    int nv;                // variables the set evolves (the fewest an FV patch of it carries)
+    int flags;             // EXA_PDE_FLAG_*
+    int max_dim;           // dimensions the set's terms are written for.  Informational: no entry reads it -- a plan's creation does not refuse a 2-D
+                           // set in 3-D, the slots do at the call (fv_run, fv_maxeig_run, fv_muscl_entry), as before the table existed
+    int k_dmp;             // variables the limiter's discrete maximum principle watches: bounds[cell][2 k_dmp]
+    const DgLaunchTable* dg[4];                                    // [dim], null: not built
+    // fv_rusanov.hip: EXA_FV_FAITHFUL / EXA_FV_RUSANOV update; CFL scan -- max over the INTERIOR volumes of all patches and the directions of the
+    // largest eigenvalue -> lam[0] (device); flux F / eigenvalue lam of n states (X: [n][3] positions for term sets of (x, t), or null)
+    int (*fv)(const FvLaunch& a);
+    int (*fv_maxeig)(int dim, int P, int H, int V, long n_patches, const double* Q, double* lam, const double* centre, double t, double h, hipStream_t s);
+    int (*pde_eval)(int normal, long n, int stride, const double* Q, double* F, double* lam, const double* X, double t, hipStream_t s);
+    // fv_muscl.hip / fv_muscl_user.hip: the EXA_FV_MUSCL_HANCOCK update in a.form
+    int (*fv_muscl)(const FvLaunch& a);
+    // lim_user.hip: the set's own a-posteriori criterion -- u^n -> u_old (may be null) + bounds; candidate + bounds (+ neighbour blocks' bounds) -> mask
+    // bytes.  Null: the Euler-layout criterion of limiter.hip (limiter_snapshot / limiter_detect)
+    int (*lim_snapshot)(int dim, int N, long ncells, const double* u, double* u_old, double* bounds, hipStream_t s);
+    int (*lim_detect)(int dim, int N, const long* nc, const double* u, const double* bounds, const LimGhosts* ghosts, const int* kinds, double d0,
+                      double eps, double floor, unsigned char* mask, hipStream_t s);
+    // limiter.hip / lim_conserve_user.hip, the conservative DG / FV interface: FV face fluxes of the listed patches at the DG face nodes,
+    // fvflux[slot][d*2+side][var][node]; their lift into the untroubled (mask == 0) face neighbours of the listed cells, one launch per (axis, side)
+    int (*lim_face_flux)(int dim, int N, const double* patch, const long* cells, long n, double* fvflux, const double* Rdev, hipStream_t s);
+    int (*lim_interface_correct)(int dim, int N, const long* nc, double* u, const double* trace, const long* cells, long n, const unsigned char* mask,
+                                 const int* kinds, const double* fvflux, double dt, const double* dx, const double* w, const double* phiL,
+                                 const double* phiR, hipStream_t s);
+};
+// capi.cpp: null with "unknown pde %d" / "pde %d is not registered"
+const PdeKernels* pde_kernels(int pde);
+// the built-in sets' slices, tab[pde]: fv_rusanov.hip, fv_muscl.hip, limiter.hip
+void fv_fill_builtin(PdeKernels* tab);
+void fv_muscl_fill_builtin(PdeKernels* tab);
+void limiter_fill_builtin(PdeKernels* tab);
 
 // fv_muscl.hip (exa_fv_muscl.hpp): the second-order MUSCL-Hancock patch update, EXA_FV_MUSCL_HANCOCK.  Its LDS plan: per patch the window
 // (P + 4)^dim x V and the predictor's increments (P + 2)^dim x n_real, 8 B each; patches whose plan stays within 64 KiB share a 256-thread
@@ -154,30 +186,6 @@ inline bool fv_muscl_stream_plan(int P, int n_real, int V, FvMusclPlan* pl) {
     if (six <= FV_MUSCL_LDS_AVAILABLE) { pl->ring = 6; pl->lds = six; }
     return true;
 }
-// out != nullptr: out of place (QOut halo-less); slot: as fv_launch
-int fv_muscl_launch(int dim, int P, int H, int n_real, int n_aux, long n_patches, int pde, double* Q, double dt, double h, const long* slot,
-                    hipStream_t s, double* out);
-int user_fv_muscl_launch(int pde, int dim, int P, int H, int n_real, int n_aux, long n_patches, double* Q, double dt, double h, const long* slot,
-                         hipStream_t s, double* out);
-// the same update by the plane-streaming kernel (3-D; a plan created with exa_fv_plan_create_streamed that is_streamed): same arguments, same results
-int fv_muscl_stream_launch(int P, int H, int n_real, int n_aux, long n_patches, int pde, double* Q, double dt, double h, const long* slot, hipStream_t s,
-                           double* out);
-int user_fv_muscl_stream_launch(int pde, int P, int H, int n_real, int n_aux, long n_patches, double* Q, double dt, double h, const long* slot,
-                                hipStream_t s, double* out);
-// the GRID step of this mode (exa_fv_grid_step_muscl_device; fv_muscl_grid_kernel): Q and out halo-less [patch][P^dim][V], the patches the cells of
-// the grid g (row-major); bstate == null: every domain face periodic, else face (axis, side) is of kind bkind[axis * 2 + side] (FV_FACE_*) with its V
-// doubles of data in bstate[(axis * 2 + side) * V ..]; lam (optional): receives the largest eigenvalue of the NEW states (zeroed by the launcher)
-struct FvMusclGrid {
-    int g[3];
-    int bkind[6];
-    const double* bstate;
-    double* lam;
-};
-int fv_muscl_grid_launch(int dim, int P, int n_real, int n_aux, long n_patches, int pde, const double* Q, double* out, double dt, double h,
-                         const FvMusclGrid* grid, hipStream_t s);
-int user_fv_muscl_grid_launch(int pde, int dim, int P, int n_real, int n_aux, long n_patches, const double* Q, double* out, double dt, double h,
-                              const FvMusclGrid* grid, hipStream_t s);
-
 void set_error(const char* fmt, ...);
 
 }  // namespace exa

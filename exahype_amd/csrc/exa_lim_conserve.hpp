@@ -263,4 +263,11 @@ static int lim_interface_correct_all(int dim, int N, const long* nc, double* u, 
     return 0;
 }
 
+// this unit's slice of a term set's table (exa_launch.hpp PdeKernels)
+template <class PDE>
+static void lim_conserve_fill(PdeKernels* k) {
+    k->lim_face_flux = lim_face_flux_all<PDE>;
+    k->lim_interface_correct = lim_interface_correct_all<PDE>;
+}
+
 }  // namespace exa

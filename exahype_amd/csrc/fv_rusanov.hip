@@ -1422,106 +1422,82 @@ static int fv_mode(int mode, int P, int H, int m, int V, long n_patches, double*
 }
 
 // the launch's arguments as the kernels take them
-static FvCellData make_cd(double* out, const double* centre, double t, double h, const FvGridArgs* grid) {
-    FvCellData cd{out, centre, t, h, nullptr, {1, 1, 1}, nullptr, 0, {0, 0, 0, 0, 0, 0}};
-    if (grid) { cd.out = grid->out; cd.bstate = grid->bstate; cd.lam = grid->lam; cd.grid_on = 1; for (int a = 0; a < 3; a++) cd.g[a] = grid->g[a]; for (int f = 0; f < 6; f++) cd.bkind[f] = grid->bkind[f]; }
+static FvCellData make_cd(const FvLaunch& a) {
+    FvCellData cd{a.out, a.centre, a.t, a.h, nullptr, {1, 1, 1}, nullptr, 0, {0, 0, 0, 0, 0, 0}};
+    if (const FvGrid* grid = a.grid) { cd.bstate = grid->bstate; cd.lam = grid->lam; cd.grid_on = 1; for (int d = 0; d < 3; d++) cd.g[d] = grid->g[d]; for (int f = 0; f < 6; f++) cd.bkind[f] = grid->bkind[f]; }
     return cd;
+}
+
+// ---- this unit's slice of a term set's table (exa_launch.hpp PdeKernels): one template for the built-in and the generated sets ----------------
+template <class PDE>
+static int fv_run(const FvLaunch& a) {
+    const FvCellData cd = make_cd(a);
+    const int V = a.n_real + a.n_aux;
+    if (a.grid && a.grid->lam) {
+        hipError_t e0 = hipMemsetAsync(a.grid->lam, 0, sizeof(double), a.stream);
+        if (e0 != hipSuccess) { set_error("memset: %s", hipGetErrorString(e0)); return -2; }
+    }
+    if (a.n_real > MAXV) { set_error("n_real = %d exceeds %d", a.n_real, MAXV); return -1; }
+    if (a.n_patches <= 0) return 0;
+    if (a.dim == 2) return fv_mode<2, PDE>(a.mode, a.P, a.H, a.n_real, V, a.n_patches, a.Q, a.dt, a.h, a.slot, a.stream, cd);
+    if constexpr (PDE::MAXDIM >= 3) {
+        if (a.dim == 3) return fv_mode<3, PDE>(a.mode, a.P, a.H, a.n_real, V, a.n_patches, a.Q, a.dt, a.h, a.slot, a.stream, cd);
+    }
+    set_error("FV Rusanov: the term set has no FV kernel for dim %d", a.dim);
+    return -1;
+}
+
+template <class PDE>
+static int fv_maxeig_run(int dim, int P, int H, int V, long n_patches, const double* Q, double* lam, const double* centre, double t, double h, hipStream_t s) {
+    if (dim == 2) return fv_maxeig<2, PDE>(P, H, V, n_patches, Q, lam, s, centre, t, h);
+    if constexpr (PDE::MAXDIM >= 3) {
+        if (dim == 3) return fv_maxeig<3, PDE>(P, H, V, n_patches, Q, lam, s, centre, t, h);
+    }
+    set_error("FV max eigenvalue: the term set has no FV kernel for dim %d", dim);
+    return -1;
+}
+
+template <class PDE>
+static int pde_eval_run(int normal, long n, int stride, const double* Q, double* F, double* lam, const double* X, double t, hipStream_t s) {
+    if (n <= 0) return 0;
+    hipLaunchKernelGGL((pde_eval_kernel<PDE>), dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, normal, n, stride, Q, F, lam, X, t);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) { set_error("pde_eval launch: %s", hipGetErrorString(e)); return -2; }
+    return 0;
+}
+
+// PDE: the set as the patch kernels see it; EVAL: as pde_eval sees it (the advection: every variable there, one here)
+template <class PDE, class EVAL = PDE>
+static void fv_fill(PdeKernels* k) {
+    k->fv = fv_run<PDE>;
+    k->fv_maxeig = fv_maxeig_run<PDE>;
+    k->pde_eval = pde_eval_run<EVAL>;
 }
 
 #ifdef EXA_USER_PDE_HEADER
 }  // namespace exa
-// user-PDE side library: the same fused kernel instantiated for exa::UserPDE
-extern "C" int exa_user_nv() { return exa::UserPDE::NV; }
+// user-PDE side library: the same kernels instantiated for exa::UserPDE.  This unit is in every side library: its filler brings the constants too.
 // include/exahype_hip.h EXA_PDE_FLAG_*: bit 0: the terms depend on position / time (HAS_XT), bit 1: the term set carries a non-conservative product
 // (HAS_NCP), bit 2: its own admissibility criterion (HAS_ADMISSIBLE), bit 3: the limiter's conservative interface (HAS_CONSERVATIVE_INTERFACE),
 // bit 4: the MUSCL-Hancock patch update (HAS_MUSCL_HANCOCK; fv_muscl_user.hip), bit 5: ... with the set's source / ncp in it (HAS_MUSCL_TERMS)
-extern "C" int exa_user_pde_flags() {
-    return (exa::pde_has_xt<exa::UserPDE>::value ? 1 : 0) | (exa::pde_has_ncp<exa::UserPDE>::value ? 2 : 0) | (exa::pde_has_admissible<exa::UserPDE>::value ? 4 : 0) |
-           (exa::pde_has_conservative_interface<exa::UserPDE>::value ? 8 : 0) | (exa::pde_has_muscl_hancock<exa::UserPDE>::value ? 16 : 0) |
-           (exa::pde_has_muscl_terms<exa::UserPDE>::value ? 32 : 0);
-}
-extern "C" int exa_user_fv_maxeig(int dim, int P, int H, int n_real, int n_aux, long n_patches, const double* Q, double* lam, void* stream,
-                                  const double* centre, double t, double h) {
+extern "C" int exa_user_fill_fv(exa::PdeKernels* k) {
     using namespace exa;
-    if (dim == 2) return fv_maxeig<2, UserPDE>(P, H, n_real + n_aux, n_patches, Q, lam, (hipStream_t)stream, centre, t, h);
-    if (dim == 3 && UserPDE::MAXDIM >= 3) return fv_maxeig<3, UserPDE>(P, H, n_real + n_aux, n_patches, Q, lam, (hipStream_t)stream, centre, t, h);
-    set_error("user PDE: no FV kernel for dim %d", dim);
-    return -1;
-}
-extern "C" int exa_user_fv_launch(int mode, int dim, int P, int H, int n_real, int n_aux, long n_patches, double* Q, double dt,
-                                  double h, const long* slot, void* stream, double* out, const double* centre, double t, const void* grid) {
-    using namespace exa;
-    const FvCellData cd = make_cd(out, centre, t, h, static_cast<const FvGridArgs*>(grid));
-    const int V = n_real + n_aux;
-    if (n_real > MAXV || n_real < UserPDE::NV) { set_error("user PDE evolves %d variables; n_real = %d", UserPDE::NV, n_real); return -1; }
-    if (n_patches <= 0) return 0;
-    if (dim == 2) return fv_mode<2, UserPDE>(mode, P, H, n_real, V, n_patches, Q, dt, h, slot, (hipStream_t)stream, cd);
-    if (dim == 3 && UserPDE::MAXDIM >= 3) return fv_mode<3, UserPDE>(mode, P, H, n_real, V, n_patches, Q, dt, h, slot, (hipStream_t)stream, cd);
-    set_error("user PDE: no FV kernel for dim %d", dim);
-    return -1;
-}
-extern "C" int exa_user_pde_eval(int normal, long n, int stride, const double* Q, double* F, double* lam, void* stream, const double* X, double t) {
-    using namespace exa;
-    if (n <= 0) return 0;
-    hipLaunchKernelGGL((pde_eval_kernel<UserPDE>), dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, normal, n, stride, Q, F, lam, X, t);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) { set_error("pde_eval launch: %s", hipGetErrorString(e)); return -2; }
+    if (k->abi != PDE_KERNELS_ABI) return PDE_KERNELS_ABI;
+    k->nv = UserPDE::NV;
+    k->flags = (pde_has_xt<UserPDE>::value ? 1 : 0) | (pde_has_ncp<UserPDE>::value ? 2 : 0) | (pde_has_admissible<UserPDE>::value ? 4 : 0) |
+               (pde_has_conservative_interface<UserPDE>::value ? 8 : 0) | (pde_has_muscl_hancock<UserPDE>::value ? 16 : 0) |
+               (pde_has_muscl_terms<UserPDE>::value ? 32 : 0);
+    k->max_dim = UserPDE::MAXDIM;
+    fv_fill<UserPDE>(k);
     return 0;
 }
 namespace exa {
 #else
-int fv_maxeig_launch(int dim, int P, int H, int n_real, int n_aux, long n_patches, int pde, const double* Q, double* lam, hipStream_t s,
-                     const double* centre, double t, double h) {
-    const int V = n_real + n_aux;
-    if (pde >= 100) return user_fv_maxeig(pde, dim, P, H, n_real, n_aux, n_patches, Q, lam, s, centre, t, h);
-    if (dim == 2) {
-        if (pde == 0) return fv_maxeig<2, EulerRef2D>(P, H, V, n_patches, Q, lam, s, centre, t, h);
-        if (pde == 1) return fv_maxeig<2, Euler>(P, H, V, n_patches, Q, lam, s, centre, t, h);
-        if (pde == 2) return fv_maxeig<2, Advection<MAXV>>(P, H, V, n_patches, Q, lam, s, centre, t, h);
-    } else if (dim == 3) {
-        if (pde == 1) return fv_maxeig<3, Euler>(P, H, V, n_patches, Q, lam, s, centre, t, h);
-        if (pde == 2) return fv_maxeig<3, Advection<MAXV>>(P, H, V, n_patches, Q, lam, s, centre, t, h);
-    }
-    set_error("FV max eigenvalue: no kernel for dim %d, pde %d", dim, pde);
-    return -1;
+void fv_fill_builtin(PdeKernels* tab) {
+    fv_fill<EulerRef2D>(&tab[0]);
+    fv_fill<Euler>(&tab[1]);
+    fv_fill<Advection<MAXV>, Advection<1>>(&tab[2]);
 }
-
-int fv_launch(int mode, int dim, int P, int H, int n_real, int n_aux, long n_patches, int pde, double* Q, double dt,
-              double h, const long* slot, hipStream_t s, double* out, const double* centre, double t, const FvGridArgs* grid) {
-    const int V = n_real + n_aux;
-    const FvCellData cd = make_cd(out, centre, t, h, grid);
-    if (grid && grid->lam) {
-        hipError_t e0 = hipMemsetAsync(grid->lam, 0, sizeof(double), s);
-        if (e0 != hipSuccess) { set_error("memset: %s", hipGetErrorString(e0)); return -2; }
-    }
-    if (n_real > MAXV) { set_error("n_real = %d exceeds %d", n_real, MAXV); return -1; }
-    if (n_patches <= 0) return 0;
-    if (pde >= 100) return user_fv_launch(pde, mode, dim, P, H, n_real, n_aux, n_patches, Q, dt, h, slot, s, out, centre, t, grid);
-    if (dim == 2) {
-        if (pde == 0) return fv_mode<2, EulerRef2D>(mode, P, H, n_real, V, n_patches, Q, dt, h, slot, s, cd);
-        if (pde == 1) return fv_mode<2, Euler>(mode, P, H, n_real, V, n_patches, Q, dt, h, slot, s, cd);
-        if (pde == 2) return fv_mode<2, Advection<MAXV>>(mode, P, H, n_real, V, n_patches, Q, dt, h, slot, s, cd);
-    } else if (dim == 3) {
-        if (pde == 1) return fv_mode<3, Euler>(mode, P, H, n_real, V, n_patches, Q, dt, h, slot, s, cd);
-        if (pde == 2) return fv_mode<3, Advection<MAXV>>(mode, P, H, n_real, V, n_patches, Q, dt, h, slot, s, cd);
-    }
-    set_error("FV Rusanov: no kernel for dim %d, pde %d", dim, pde);
-    return -1;
-}
-
-int pde_eval_launch(int pde, int normal, long n, int stride, const double* Q, double* F, double* lam, hipStream_t s, const double* X, double t) {
-    if (n <= 0) return 0;
-    if (pde >= 100) return user_pde_eval(pde, normal, n, stride, Q, F, lam, s, X, t);
-    const dim3 grid((unsigned)((n + 255) / 256));
-    if (pde == 0) hipLaunchKernelGGL((pde_eval_kernel<EulerRef2D>), grid, dim3(256), 0, s, normal, n, stride, Q, F, lam, X, t);
-    else if (pde == 1) hipLaunchKernelGGL((pde_eval_kernel<Euler>), grid, dim3(256), 0, s, normal, n, stride, Q, F, lam, X, t);
-    else if (pde == 2) hipLaunchKernelGGL((pde_eval_kernel<Advection<1>>), grid, dim3(256), 0, s, normal, n, stride, Q, F, lam, X, t);
-    else { set_error("unknown pde %d", pde); return -1; }
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) { set_error("pde_eval launch: %s", hipGetErrorString(e)); return -2; }
-    return 0;
-}
-
 #endif
 
 }  // namespace exa

@@ -717,20 +717,12 @@ int limiter_detect(int dim, int N, int nv, const long* nc, const double* u, cons
 
 // ------------------------------------------------------------------------------------------------------------------
 // Conservative DG / FV interface: the kernels live in exa_lim_conserve.hpp, templates over the term set.  Here: the
-// built-in Euler and advection sets.  A generated term set that asks for the interface instantiates them in its side library
-// (lim_conserve_user.hip).
+// built-in Euler (5 variables) and advection (1 variable) sets; EulerRef2D has none.  A generated term set that asks for the interface
+// instantiates them in its side library (lim_conserve_user.hip).
 // ------------------------------------------------------------------------------------------------------------------
-// pde: 1 Euler (5 variables), 2 advection (1 variable); the C-ABI entry has refused everything else
-int limiter_face_flux(int dim, int N, int pde, const double* patch, const long* cells, long n, double* fvflux, const double* Rdev, hipStream_t s) {
-    return pde == 1 ? lim_face_flux_all<Euler>(dim, N, patch, cells, n, fvflux, Rdev, s)
-                    : lim_face_flux_all<Advection<1>>(dim, N, patch, cells, n, fvflux, Rdev, s);
-}
-
-int limiter_interface_correct(int dim, int N, int pde, const long* nc, double* u, const double* trace, const long* cells, long n,
-                              const unsigned char* mask, const int* kinds, const double* fvflux, double dt, const double* dx,
-                              const double* w, const double* phiL, const double* phiR, hipStream_t s) {
-    return pde == 1 ? lim_interface_correct_all<Euler>(dim, N, nc, u, trace, cells, n, mask, kinds, fvflux, dt, dx, w, phiL, phiR, s)
-                    : lim_interface_correct_all<Advection<1>>(dim, N, nc, u, trace, cells, n, mask, kinds, fvflux, dt, dx, w, phiL, phiR, s);
+void limiter_fill_builtin(PdeKernels* tab) {
+    lim_conserve_fill<Euler>(&tab[1]);
+    lim_conserve_fill<Advection<1>>(&tab[2]);
 }
 
 }  // namespace exa

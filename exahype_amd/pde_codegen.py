@@ -153,9 +153,9 @@ class SympyPDE:
 
         muscl_hancock=True (keyword only): the term set asks for the second-order MUSCL-Hancock patch update (FVRusanovKernel / FVPatchGrid /
         HIPPrinter with mode FV_MUSCL_HANCOCK).  The generated struct then carries HAS_MUSCL_HANCOCK and the side library one more unit
-        (csrc/fv_muscl_user.hip: exa_user_fv_muscl_launch and, for the one-launch grid step FVPatchGrid(fused=FUSED_EDGES),
-        exa_user_fv_muscl_grid_launch; a cached library from before that entry still registers, the grid step asks for a rebuild; and, for
-        3-D patches walked plane by plane (FVRusanovKernel(stream_planes=...)), exa_user_fv_muscl_stream_launch, resolved the same way).  The scheme -- slopes, half-step predictor, Rusanov flux of the predicted face
+        (csrc/fv_muscl_user.hip: one entry for the resident update, the one-launch grid step FVPatchGrid(fused=FUSED_EDGES) and the 3-D patches
+        walked plane by plane (FVRusanovKernel(stream_planes=...)); exa_register_pde refuses a library whose kernel table has another ABI
+        number and asks for a rebuild).  The scheme -- slopes, half-step predictor, Rusanov flux of the predicted face
         states -- is written for conservative terms of the state alone: terms that depend on position / time, an ncp or a source raise
         ValueError.  Without the keyword the generated source, the cache key and the build are what they were, and a plan in that mode on such a
         term set is refused.
@@ -688,9 +688,8 @@ struct UserPDE {
         if self.conservative_interface:                                # (... and so is the unit of the conservative interface)
             for f in ("lim_conserve_user.hip", "exa_lim_conserve.hpp", "exa_lim_detect.hpp"):
                 h.update(open(os.path.join(CSRC, f), "rb").read())
-        if self.muscl_hancock:                                         # (... and the unit of the second-order patch update: a library cached
-            for f in ("fv_muscl_user.hip", "exa_fv_muscl.hpp"):        # before an entry was added to it -- exa_user_fv_muscl_grid_launch,
-                                                                       # exa_user_fv_muscl_stream_launch -- has another key and is rebuilt)
+        if self.muscl_hancock:                                         # (... and the unit of the second-order patch update)
+            for f in ("fv_muscl_user.hip", "exa_fv_muscl.hpp"):
                 h.update(open(os.path.join(CSRC, f), "rb").read())
         h.update(open(os.path.join(os.path.dirname(os.path.abspath(__file__)), "build.py"), "rb").read())      # (compiler flags)
         h.update(repr(self.dg_flags).encode())
@@ -723,11 +722,11 @@ struct UserPDE {
                  ("dg_inst.hip", "dg2b.o", ["-DEXA_DIM=2", "-DEXA_UNIT_B"])]
         if self.max_dim >= 3:
             units += [("dg_inst.hip", "dg3.o", ["-DEXA_DIM=3", "-DEXA_UNIT_A"] + sched), ("dg_inst.hip", "dg3b.o", ["-DEXA_DIM=3", "-DEXA_UNIT_B"])]
-        if self.adm_exprs is not None:                                 # the term set's own a-posteriori detector (exa_user_lim_snapshot / _detect)
+        if self.adm_exprs is not None:                                 # the term set's own a-posteriori detector (exa_lim_snapshot / _detect)
             units.append(("lim_user.hip", "lim.o", []))
         if self.conservative_interface:                                # its instantiation of exa_lim_face_flux / exa_lim_interface_correct
             units.append(("lim_conserve_user.hip", "limc.o", []))
-        if self.muscl_hancock:                                         # its instantiation of the MUSCL-Hancock patch update (exa_user_fv_muscl_launch)
+        if self.muscl_hancock:                                         # its instantiation of the MUSCL-Hancock patch update
             units.append(("fv_muscl_user.hip", "fvm.o", ["-ffp-contract=off"]))
         procs = [(o, subprocess.Popen(common + extra + ["-c", os.path.join(CSRC, src), "-o", os.path.join(d, o)],
                                       stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, env=_build.compiler_env())) for src, o, extra in units]

@@ -88,7 +88,9 @@ int exa_device_count(int* count);
 /* ---- user PDE term sets ------------------------------------------------------- */
 /* The reference resolves `Flux` / `maxEigenvalue` at link time to user C++ (Unit test/Functions.h:2-3).
  * Here a user term set is a side library generated from SymPy expressions and compiled with hipcc
- * (exahype_amd/pde_codegen.py); registering it yields a pde id >= 100 usable wherever EXA_PDE_* is. */
+ * (exahype_amd/pde_codegen.py); registering it yields a pde id >= 100 usable wherever EXA_PDE_* is.  EXA_ERR_INVALID: the file does not load, it is
+ * no such library, a unit its flags ask for is missing, or it was built against another layout of the kernel table (one ABI number, checked
+ * here: the message says to rebuild the term set). */
 int exa_register_pde(const char* library_path, int* pde_id);
 /* What a registered term set carries (0 for the built-in ones): EXA_PDE_FLAG_XT -- its terms depend on position / time (they see the
  * coordinates the kernels hand them; exa_pde_eval_device and exa_dg_max_eigenvalue, which have none, evaluate them at x = 0, t = 0:
@@ -133,7 +135,7 @@ int exa_fv_plan_create(int device, int mode, int dim, int patch_size, int halo_s
  *   EXA_FV_STREAM_IF_NEEDED  the resident plan where it fits, the streamed one where not (3-D; in 2-D as NEVER)
  *   EXA_FV_STREAM_ALWAYS     the streamed plan wherever it exists (tests, measurements)
  * EXA_ERR_INVALID: a non-zero stream_planes with another mode; ALWAYS in 2-D; a shape whose streamed plan does not fit (the message names the bytes
- * of both plans); an unknown value; a registered term set whose side library was built before exa_user_fv_muscl_stream_launch existed (rebuild it).
+ * of both plans); an unknown value.
  * A streamed plan is served by every exa_fv_time_step_* entry and by exa_fv_max_eigenvalue; exa_fv_grid_step_muscl_device refuses it (the
  * one-launch gather is not built for this form: use the two-pass form on the array with halo). */
 #define EXA_FV_STREAM_NEVER 0
@@ -221,7 +223,7 @@ int exa_fv_grid_step_device_bc(exa_fv_plan* plan, const double* Q_dev, double* Q
  * exa_fv_max_eigenvalue(plan, QNext_dev, 1, ...) (a NaN survives).  halo_size of the plan is not used (the arrays have none).
  * EXA_ERR_INVALID, with a message that names the way out: a NULL plan or pointer; a plan of another mode; patch_size < 2 (the second layer would
  * belong to the neighbour's neighbour: the two-pass form serves it); QNext_dev == Q_dev; a product of grid that is not n_patches; a kind outside
- * 0 .. 2; a non-periodic kind without data; h <= 0; a registered term set whose side library was built before this entry existed (rebuild it). */
+ * 0 .. 2; a non-periodic kind without data; h <= 0. */
 int exa_fv_grid_step_muscl_device(exa_fv_plan* plan, const double* Q_dev, double* QNext_dev, const long* grid, const int* face_kind,
                                   const double* face_data_dev, double dt, double h, double* lambda_next_dev, void* stream);
 /* CFL scan of a patch array: max over the INTERIOR volumes of all patches and over the directions of the largest eigenvalue -> lambda_dev[0]

@@ -317,7 +317,7 @@ def test_grid_step_arguments_are_checked():
 
 @pytest.mark.gpu
 def test_grid_step_with_a_generated_term_set_and_cfl_loop():
-    """The grid step through a user library (exa_user_fv_launch with the grid arguments) == the two-pass form; run() with the fused CFL scan takes
+    """The grid step through a user library (its fv slot with the grid arguments) == the two-pass form; run() with the fused CFL scan takes
     the same steps as run() with a scan pass per step."""
     from exahype_amd import solvers as exa
     from tests.test_user_pde import swe, swe_state

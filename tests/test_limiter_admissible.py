@@ -1,5 +1,5 @@
 """A-posteriori subcell limiting with the term set's own criterion: SympyPDE(admissible=..., dmp=...), the generated detection kernels
-(exa_user_lim_snapshot / exa_user_lim_detect behind exa_lim_snapshot / exa_lim_detect), exa_lim_bounds_count and SubcellLimiter.
+(the side library's unit lim_user.hip behind exa_lim_snapshot / exa_lim_detect), exa_lim_bounds_count and SubcellLimiter.
 
 CPU: code generation and its refusals, the unchanged source of term sets without the keywords, the C-ABI entry, the numpy restatement
 (tests/limiter_admissible_ref.py) against limiter_mood_ref with the Euler criterion, and why the feature exists: a smooth shallow-water

@@ -1,5 +1,5 @@
 """Conservative DG / FV interface of the a-posteriori subcell limiter for GENERATED term sets: SympyPDE(conservative_interface=True), the
-marker and EXA_PDE_FLAG_CONSERVATIVE, the side library's unit lim_conserve_user.hip (exa_user_lim_face_flux / exa_user_lim_interface_correct
+marker and EXA_PDE_FLAG_CONSERVATIVE, the side library's unit lim_conserve_user.hip (its filler exa_user_fill_lim_conserve, the slots
 behind exa_lim_face_flux / exa_lim_interface_correct) and SubcellLimiter.step / step_a_posteriori / run with conservative=True.
 
 CPU: keyword, marker and refusals; the unit compiles against the generated shallow-water header and against a 24-variable system (whose
@@ -318,8 +318,8 @@ def test_flag_and_entries_of_the_side_library():
     assert lib.exa_pde_flags(reaction_cons().register()) == 8
     assert lib.exa_pde_flags(swe_lim().register()) == 4
     so = C.CDLL(swe_cons().build())
-    assert hasattr(so, "exa_user_lim_face_flux") and hasattr(so, "exa_user_lim_interface_correct")
-    assert not hasattr(C.CDLL(swe_lim().build()), "exa_user_lim_face_flux")
+    assert hasattr(so, "exa_user_fill_lim_conserve")
+    assert not hasattr(C.CDLL(swe_lim().build()), "exa_user_fill_lim_conserve")
 
 
 @gpu
